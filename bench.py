@@ -37,6 +37,17 @@ around a launch adds ~4.6 µs of dispatch gap to its step (tools/gap_probe.py:
 0.2888 ms per c3 step without events, 0.2981 with the kernels' own events on
 every step), which would otherwise be charged to `value`.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline needs:
+set up, warm up, time the K steps, print the line (`value`, `ms_per_step`,
+the kernels' own windows of the sampled steps).  `--full` adds everything
+else to the same line, as before: the output checks (torch XOR of every line,
+every erased segment back bit-exact, the reference's digests), the c4_strong,
+c5, c3full and wire sub-objects, the copy and r : w ceilings and the CPU
+baseline; `verified`, `copy_ceiling_GBps` and `mix_ceiling` are null without
+it.  `--dump-outputs DIR` writes the last timed step's outputs (a fixed,
+seeded sample of the groups) as DIR/<name>.npy, so two builds can be compared
+output for output.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -334,6 +345,42 @@ class Workload:
                              self.fsize[g0:g1].view(torch.uint8).reshape(n, -1)], dim=1)
             h.update(rec.cpu().numpy().tobytes())
         return h.hexdigest()
+
+
+DUMP_SEED = 20241  # --dump-outputs: the sampled groups are the same in every run
+DUMP_BUDGET = 48 << 20  # bytes of float32 per rank (the option's limit is 64 MB in all)
+
+
+def dump_outputs(outdir, enc, dec, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as
+    DIR/<name>.npy -- the encode's parity, meta, fec_data_size and status of
+    the set it encoded (`enc`), the decode's recovered segments, headers,
+    indices and masks of the set it recovered (`dec`; in place: the received
+    shards and headers it filled) -- over a fixed, seeded sample of the groups
+    (`groups.npy`, float64: their indices within this rank's batch), byte
+    values as float32, the masks as float64.  The inputs are seeded, so two
+    builds run with the same arguments write comparable files.  Ranks other
+    than 0 prefix their files with `rank<r>_`."""
+    S, n = enc.S, enc.n
+    per_group = n * (S + 22) + (2 * (S + 21) + 2 if dec.dense else dec.k * (S + 20) + 2)
+    m = min(enc.G, max(1, DUMP_BUDGET // (4 * per_group)))
+    gsel = np.sort(np.random.default_rng(DUMP_SEED).choice(enc.G, m, replace=False))
+    idx = torch.from_numpy(gsel).to(enc.shards.device)
+    out = {"parity": enc.parity[idx][:, :, :S], "meta": enc.meta[idx], "fec_data_size": enc.fsize[idx],
+           "status": enc.status[idx]}
+    if dec.dense:
+        out.update(out_shards=dec.out_shards[idx][:, :, :S], out_hdr=dec.out_hdr[idx], out_index=dec.out_index[idx])
+    else:
+        out.update(rx=dec.rx[idx][:, :, :S], rx_hdr=dec.rx_hdr[idx])
+    arrays = {name: t.cpu().numpy().astype(np.float32) for name, t in out.items()}
+    arrays["recovered"] = dec.recovered[idx].cpu().numpy().view(np.uint64).astype(np.float64)
+    arrays["groups"] = gsel.astype(np.float64)
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    prefix = f"rank{rank}_" if rank else ""
+    for name, a in arrays.items():
+        np.save(outdir / f"{prefix}{name}.npy", np.ascontiguousarray(a))
+    return sum(a.nbytes for a in arrays.values())
 
 
 def copy_ceiling(lib, device, nbytes=1 << 30, reps=10):
@@ -938,7 +985,17 @@ def main():
     ap.add_argument("--no-wire", action="store_true", help="skip the wire sub-object (§8(f1) kernels)")
     ap.add_argument("--sub-steps", type=int, default=80,
                     help="timed steps of the c5 / c3full sub-objects (config c3 only; 0 = skip them)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the output checks against torch XORs and the "
+                         "reference's digests, the c4_strong / c5 / c3full / wire sub-objects, the copy and r : w "
+                         "ceilings, the CPU baseline (each still under its own option above)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's outputs (a fixed, seeded sample of the "
+                         "groups) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
+    verify = args.full and not args.no_verify
 
     # --gpus N without a launcher: start N ranks under torchrun as a child
     # process (nothing here has touched the GPU yet), exit with its code
@@ -1009,9 +1066,14 @@ def main():
     elapsed, t_enc, t_dec, own_enc, own_dec, window = time_steps(lib, sets, args.steps, args.warmup, stream, dist,
                                                                  args.timing, args.hot_decode)
     ranks = gather_objects(dist, dict(rank=rank, local_rank=local, **device_identity(device)))
+    if args.dump_outputs:  # the sets of the last timed step (time_steps' rotation), before anything else runs
+        last = args.warmup + args.steps - 1
+        dumped = dump_outputs(args.dump_outputs, sets[last % nset],
+                              sets[(last if args.hot_decode else last - 1) % nset], rank, world)
+        log(f"dumped {dumped} bytes of outputs to {args.dump_outputs}")
 
     verified, digest_ok = None, None
-    if not args.no_verify:
+    if verify:
         verified = all(ws.verify() for ws in sets)
         # the reference's digest of exactly these groups, where the golden file holds one
         want = None
@@ -1030,24 +1092,23 @@ def main():
         vt = torch.tensor([1 if verified in (None, True) else 0, 0 if digest_ok is False else 1,
                            1 if digest_ok is True else 0], dtype=torch.int32)
         dist.all_reduce(vt, op=dist.ReduceOp.MIN)
-        verified = None if args.no_verify else bool(vt[0].item())
-        digest_ok = None if args.no_verify else (False if not vt[1].item() else (True if vt[2].item() else None))
+        verified = None if not verify else bool(vt[0].item())
+        digest_ok = None if not verify else (False if not vt[1].item() else (True if vt[2].item() else None))
 
     # BASELINE configs[3] beside the weak headline (default run only): the 1M-group strong split
     c4 = None
-    if cfg_name == "c3" and args.c4_steps > 0 and not args.lib:
+    if args.full and cfg_name == "c3" and args.c4_steps > 0 and not args.lib:
         log("c4 strong split ...")
-        c4 = c4_strong(lib, device, stream, dist, world, rank, args.protect_fraction, args.c4_steps, 2,
-                       not args.no_verify)
+        c4 = c4_strong(lib, device, stream, dist, world, rank, args.protect_fraction, args.c4_steps, 2, verify)
         if c4 and c4["verified"] is False:
             verified = False
     # BASELINE configs[4] (c5) and the sender's full plan (c3full) on the same line (default run only)
     subs = {}
-    if cfg_name == "c3" and args.sub_steps > 0 and not args.lib:
+    if args.full and cfg_name == "c3" and args.sub_steps > 0 and not args.lib:
         for sub in ("c5", "c3full"):
             log(f"{sub} ...")
             subs[sub] = config_sub(lib, sub, device, stream, dist, world, rank, args.protect_fraction,
-                                   args.sub_steps, 2, not args.no_verify)
+                                   args.sub_steps, 2, verify)
             if subs[sub] and subs[sub]["verified"] is False:
                 verified = False
 
@@ -1062,8 +1123,8 @@ def main():
     achieved = w.enc_bytes / enc_mean / 1e9
     res = None
     if rank == 0:
-        ceiling = copy_ceiling(lib, device)
-        mix = encode_mix(w)
+        ceiling = copy_ceiling(lib, device) if args.full else None
+        mix = encode_mix(w) if args.full else None
         mix_gbps = mix_ceiling(lib, device, *mix) if mix else None
         workload_name = f"k{k}_r{w.n}_S{S}_G{w.G}"
         enc_kernel, dec_kernels, lines, _ = kernel_desc(w, k, S, full_plan)
@@ -1136,7 +1197,8 @@ def main():
                                 "kernels": dec_kernels,
                                 "parity_operand": "cold: written one step (>= 1.7 GB of traffic) before"
                                 if not (args.hot_decode or nset == 1) else "hot: written by this step's encode"},
-            "copy_ceiling_GBps": round(ceiling, 1),  # rfec_probe_copy, read + write bytes
+            # rfec_probe_copy, read + write bytes
+            "copy_ceiling_GBps": None if ceiling is None else round(ceiling, 1),
             "timing_window": {"rule": "value = all ranks' bytes x steps / (max over ranks of t1 - min over ranks "
                                       "of t0); t0 after the opening barrier + synchronize, t1 after the closing "
                                       "synchronize (before the closing barrier), CLOCK_MONOTONIC",
@@ -1148,8 +1210,9 @@ def main():
             "verified": verified,
             "verified_vs_reference_digest": digest_ok,
             "tuning": args.tuning,
+            "full": args.full,
         }
-        if cfg_name == "c3" and not args.no_wire and not args.lib:
+        if args.full and cfg_name == "c3" and not args.no_wire and not args.lib:
             log("wire ...")
             res["wire"] = wire_sub(lib, w, device)
             if res["wire"]["verified_round_trip"] is False or res["wire"]["verified_vs_oracle_digest"] is False:
@@ -1159,7 +1222,7 @@ def main():
         for sub, d in subs.items():
             if d is not None:
                 res[sub] = d
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             log("cpu baseline ...")
             res["cpu_baseline"] = cpu_baseline(w, args.cpu_seconds)
         print(json.dumps(res), flush=True)

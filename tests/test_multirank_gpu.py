@@ -101,11 +101,12 @@ def test_c4_split_two_ranks_one_gpu(tmp_path):
     assert lo == c["groups"]
 
 
-def _bench(*args, timeout=600):
+def _bench(*args, timeout=600, full=True):
+    """One bench.py run; --full by default: the checks and sub-objects these tests read are behind it."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True, text=True,
-                       timeout=timeout, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), *(["--full"] if full else []), *args],
+                       capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -184,6 +185,40 @@ def test_bench_one_gpu_c4_strong():
     assert set(wire["kernels"]) == {"frame_fec", "frame_seg", "parse_fec", "parse_seg"}
     assert all(0 < v["frac"] < 1 and v["launch_us"] > 0 for v in wire["kernels"].values())
     _check_window(d, 1)
+
+
+def test_bench_plain_run_and_dump(tmp_path):
+    """Without --full the line holds the headline alone (no checks, no
+    sub-objects, no ceilings, no CPU baseline), --steps sets the timed steps,
+    and --dump-outputs writes the last step's outputs over a seeded sample of
+    the groups: float32 / float64 .npy files, at most 64 MB in all, the
+    encode's status clean and fec_data_size = 1,200, the decode's two
+    recovered segments per group named by out_index in index order and by
+    the `recovered` mask."""
+    d = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out"), full=False)
+    assert d["full"] is False and d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["verified"] is None and d["verified_vs_reference_digest"] is None
+    assert d["copy_ceiling_GBps"] is None and d["roofline"]["mix_ceiling"] is None
+    assert not {"c4_strong", "c5", "c3full", "wire", "cpu_baseline"} & set(d)
+    for key in ("roofline", "decode_roofline"):
+        assert d[key]["timing"].startswith("the kernel's own") and d[key]["launch_us"] > 0
+    _check_window(d, 1)
+    a = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert set(a) == {"groups", "parity", "meta", "fec_data_size", "status", "out_shards", "out_hdr", "out_index",
+                      "recovered"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    m = len(a["groups"])
+    assert m > 1000 and np.all(np.diff(a["groups"]) > 0) and a["groups"][-1] < 65536
+    assert a["parity"].shape == (m, 3, 1200) and a["out_shards"].shape == (m, 2, 1200)
+    assert a["meta"].shape == (m, 3, 20) and a["out_hdr"].shape == (m, 2, 20)
+    assert not a["status"].any() and np.all(a["fec_data_size"] == 1200)
+    assert a["parity"].min() >= 0 and a["parity"].max() <= 255 and a["parity"].std() > 50  # xorshift bytes
+    oi = a["out_index"].astype(np.int64)
+    assert np.all(oi[:, 0] < oi[:, 1]) and oi.max() < 10
+    assert np.array_equal(a["recovered"][:, 0].astype(np.int64), (1 << oi[:, 0]) | (1 << oi[:, 1]))
+    assert not a["recovered"][:, 1].any()
 
 
 @pytest.mark.timeout(900)

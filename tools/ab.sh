@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 for r in $(seq 1 "$R"); do
   for side in a b; do
     lib=$A; [ $side = b ] && lib=$B
-    timeout -k 10 300 python bench.py --no-cpu --steps 50 --warmup 5 --lib "$lib" "$@" > "$OUT/${side}_$r.log" 2>&1
+    timeout -k 10 300 python bench.py --full --no-cpu --steps 50 --warmup 5 --lib "$lib" "$@" > "$OUT/${side}_$r.log" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "$side round $r rc=$rc"; tail -5 "$OUT/${side}_$r.log"; exit $rc; fi
     grep '^{' "$OUT/${side}_$r.log" > "$OUT/${side}_$r.json"

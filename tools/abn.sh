@@ -12,7 +12,7 @@ OUT=gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 for r in $(seq 1 "$R"); do
   for i in "${!LIBS[@]}"; do
     lib=${LIBS[$i]}; la=(); [ "$lib" != "-" ] && la=(--lib "$lib")
-    timeout -k 10 300 python bench.py --no-cpu --steps 50 --warmup 5 "${la[@]}" "$@" > "$OUT/${i}_$r.log" 2>&1
+    timeout -k 10 300 python bench.py --full --no-cpu --steps 50 --warmup 5 "${la[@]}" "$@" > "$OUT/${i}_$r.log" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "lib $i round $r rc=$rc"; tail -5 "$OUT/${i}_$r.log"; exit $rc; fi
     grep '^{' "$OUT/${i}_$r.log" > "$OUT/${i}_$r.json"

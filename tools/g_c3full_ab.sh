@@ -5,7 +5,7 @@ set -o pipefail
 TAG=${1:-c3ab}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 for r in 1 2 3; do
   for L in ${AB_LIBS:-}; do
-    timeout -k 10 150 python -u bench.py --lib tools/bin/abx/librazor_fec_$L.so --config c3full --steps 80 --warmup 5 --no-wire --no-cpu > $OUT/${L}_$r.json 2> $OUT/${L}_$r.err || { tail -20 $OUT/${L}_$r.err; exit 1; }
+    timeout -k 10 150 python -u bench.py --full --lib tools/bin/abx/librazor_fec_$L.so --config c3full --steps 80 --warmup 5 --no-wire --no-cpu > $OUT/${L}_$r.json 2> $OUT/${L}_$r.err || { tail -20 $OUT/${L}_$r.err; exit 1; }
   done
 done
 python - "$OUT" <<'PY'

@@ -15,11 +15,11 @@ if has smoke; then
   cat $OUT/smoke.log
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py > $OUT/bench.log 2>&1 || { tail $OUT/bench.log; exit 1; }
+  timeout -k 10 400 python bench.py --full > $OUT/bench.log 2>&1 || { tail $OUT/bench.log; exit 1; }
   grep '^{' $OUT/bench.log
 fi
 if has prof; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --no-cpu \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --full --no-cpu \
     > $OUT/rocprof.log 2>&1 || { tail $OUT/rocprof.log; exit 1; }
   cat $OUT/prof/run_kernel_stats.csv | cut -d, -f1-4 | head -8
 fi

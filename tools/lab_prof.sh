@@ -5,7 +5,7 @@ set -u
 TAG=$1; KEXPR=$2; CFG=$3; shift 3
 bash tools/lab_run.sh $TAG "$KEXPR" "$CFG" "$@" || exit 1
 OUT=gpurun_out/$TAG; export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --config $CFG --no-cpu --steps 30 --warmup 5 "$@" > $OUT/prof.log 2>&1 || { tail -5 $OUT/prof.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --full --config $CFG --no-cpu --steps 30 --warmup 5 "$@" > $OUT/prof.log 2>&1 || { tail -5 $OUT/prof.log; exit 1; }
 python -c "
 import csv
 for r in csv.DictReader(open('$OUT/prof/run_kernel_stats.csv')):

@@ -9,7 +9,7 @@ if [ "$KEXPR" != "-" ]; then
   tail -1 $OUT/pytest.log
 fi
 for c in $CFGS; do
-  timeout -k 10 300 python bench.py --config $c --no-cpu --steps 50 --warmup 5 "$@" > $OUT/bench_$c.log 2>&1 || { echo "$c failed"; tail -5 $OUT/bench_$c.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $c --no-cpu --steps 50 --warmup 5 "$@" > $OUT/bench_$c.log 2>&1 || { echo "$c failed"; tail -5 $OUT/bench_$c.log; exit 1; }
   grep '^{' $OUT/bench_$c.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$c', d['value'], 'enc', d['roofline']['launch_us'], d['roofline']['frac'], 'dec', d['decode_roofline']['launch_us'], d['decode_roofline']['frac'], d['verified'], d['verified_vs_reference_digest'])"
 done
 echo done

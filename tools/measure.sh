@@ -26,12 +26,12 @@ step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 LOCAL=$(bash tools/gpu_local_cpus.sh)  # the drop-in bench pinned to the GPU's NUMA node
 if [ -n "$LOCAL" ]; then step group_bench 200 taskset -c "$LOCAL" ./razor_amd/lib/fec_dropin_group_bench 2000
 else step group_bench 200 ./razor_amd/lib/fec_dropin_group_bench 2000; fi
-step bench 400 python bench.py
-step rocprof_stats 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py
-step bench_c3full 400 python bench.py --config c3full --no-cpu
-step bench_c5 400 python bench.py --config c5 --no-cpu
-step rocprof_stats_c3full 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c3full" -o run -- python bench.py --config c3full --no-cpu --steps 20 --warmup 5
-step rocprof_stats_c5 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c5" -o run -- python bench.py --config c5 --no-cpu --steps 20 --warmup 5
+step bench 400 python bench.py --full
+step rocprof_stats 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py --full
+step bench_c3full 400 python bench.py --full --config c3full --no-cpu
+step bench_c5 400 python bench.py --full --config c5 --no-cpu
+step rocprof_stats_c3full 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c3full" -o run -- python bench.py --full --config c3full --no-cpu --steps 20 --warmup 5
+step rocprof_stats_c5 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c5" -o run -- python bench.py --full --config c5 --no-cpu --steps 20 --warmup 5
 step mix 200 python tools/mix_probe.py
 if [ -n "$LOCAL" ]; then step e2e 400 taskset -c "$LOCAL" python tools/e2e_step.py --mem both
 else step e2e 400 python tools/e2e_step.py --mem both; fi

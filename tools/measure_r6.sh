@@ -22,8 +22,8 @@ LOCAL=$(bash tools/gpu_local_cpus.sh)
 PIN=(); [ -n "$LOCAL" ] && PIN=(taskset -c "$LOCAL")
 [ "${SKIP_TESTS:-0}" = 1 ] || step pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -rs --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 400 python bench.py
-step rocprof_stats 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py
+step bench 400 python bench.py --full
+step rocprof_stats 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py --full
 step rx_4096 300 "${PIN[@]}" python tools/rx_session_bench.py --frames 32768 --batch 4096 --threads 1,8 --reps 3 --out "$OUT/rx_4096.json"
 step rx_16384 300 "${PIN[@]}" python tools/rx_session_bench.py --frames 32768 --batch 16384 --threads 8 --modes async --reps 3 --out "$OUT/rx_16384.json"
 step soak_rx 400 "${PIN[@]}" python tools/soak_rx.py --seconds ${SOAK_S:-150} --out "$OUT/soak_rx.json"

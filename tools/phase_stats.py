@@ -1,5 +1,5 @@
 """Per-phase kernel statistics from a rocprofv3 kernel trace of `python
-bench.py` (the driver's default command): the FEC kernels' launches grouped
+bench.py --full` (the whole line, sub-objects included): the FEC kernels' launches grouped
 into the blocks they run in -- the headline's primed / warm-up / timed steps,
 then (after the verification kernels) the c4_strong sub-object's 65,536-group
 launches -- with calls / mean / median per kernel in each block, next to the

@@ -21,6 +21,6 @@ LOCAL=$(bash tools/gpu_local_cpus.sh)
 PIN=(); [ -n "$LOCAL" ] && PIN=(taskset -c "$LOCAL")
 [ "${SKIP_TESTS:-0}" = 1 ] || step pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -rs --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 400 python bench.py
+step bench 400 python bench.py --full
 step rx_session 400 "${PIN[@]}" python tools/rx_session_bench.py --frames 32768 --threads ${RX_THREADS:-1,4,8,16} --reps 3 --out "$OUT/rx_session.json"
 echo done | tee -a "$OUT/steps.log"

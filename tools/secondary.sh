@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 run() {  # run <name> <bench args...>
   local name=$1; shift
-  timeout -k 10 300 python bench.py --no-cpu --steps 20 --warmup 5 "$@" > "$OUT/$name.log" 2>&1
+  timeout -k 10 300 python bench.py --full --no-cpu --steps 20 --warmup 5 "$@" > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "$name rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/$name.log"; exit $rc; fi
