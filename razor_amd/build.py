@@ -30,12 +30,19 @@ HIP_SRC = [CSRC / "rfec_kernels.hip", CSRC / "rfec_probe.hip", CSRC / "rfec_wire
            CSRC / "rfec_service.hip", CSRC / "rfec_hostio.hip"]
 # built once per SIM_VIDEO_SIZE: the C host layer, by concern (rfec_host.c: errors, planner, batched device
 # and wire API; rfec_dropin.c: drop-in symbols + resident service; rfec_hostmem.c: host-memory batches;
-# rfec_sender.c: sender staging; rfec_rx.c: receiver ingestion and sessions), and the flex drop-in
-HOST_SRC = ["rfec_host.c", "rfec_dropin.c", "rfec_hostmem.c", "rfec_sender.c", "rfec_rx.c"]
+# rfec_sender.c: sender staging; the receiver: rfec_rx_sim.c one shard's arrival-order control plane,
+# rfec_rx_pool.c the replay threads, rfec_rx_plane.c the sharded plane and the host halves of compaction and of
+# the device tables, rfec_rx_dev.c the device side of ingestion, rfec_rx_session.c the sessions), and the flex
+# drop-in
+HOST_NOHIP_SRC = ["rfec_rx_sim.c", "rfec_rx_pool.c", "rfec_rx_plane.c"]  # no GPU runtime: built and tested alone
+HOST_SRC = ["rfec_host.c", "rfec_dropin.c", "rfec_hostmem.c", "rfec_sender.c", *HOST_NOHIP_SRC, "rfec_rx_dev.c",
+            "rfec_rx_session.c"]
 C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h"]
+# the receiver units' own headers: only the C host layer includes them
+HOST_HEADERS = HEADERS + [CSRC / f"rfec_rx_{u}.h" for u in ("map", "sim", "pool", "plane", "dev")]
 
 VARIANTS = {"librazor_fec.so": 1000, "librazor_fec_v1200.so": 1200}
 
@@ -82,7 +89,7 @@ def build(force: bool = False, verbose: bool = False) -> dict:
         hobjs = []
         for src in C_SRC:
             hobj = OBJDIR / f"{src.stem}_v{vsize}.o"
-            if force or _stale(hobj, [src] + HEADERS):
+            if force or _stale(hobj, [src] + HOST_HEADERS):
                 _run(["gcc", "-std=c99", "-O2", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter",
                       f"-DSIM_VIDEO_SIZE={vsize}", "-D__HIP_PLATFORM_AMD__", f"-I{ROCM / 'include'}",
                       f"-I{INCLUDE}", f"-I{CSRC}", "-c", str(src), "-o", str(hobj)])

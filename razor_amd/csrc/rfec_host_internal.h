@@ -1,8 +1,9 @@
 /*
  * rfec_host_internal.h -- declarations shared by the C host layer's
- * translation units (rfec_host.c, rfec_dropin.c, rfec_hostmem.c,
- * rfec_sender.c, rfec_rx.c).  Internal: hidden from the shared library's
- * exports.
+ * translation units that use the HIP runtime (rfec_host.c, rfec_dropin.c,
+ * rfec_hostmem.c, rfec_sender.c, rfec_rx_dev.c, rfec_rx_session.c; the
+ * receiver's host-only units rfec_rx_sim.c, rfec_rx_pool.c, rfec_rx_plane.c
+ * do without it).  Internal: hidden from the shared library's exports.
  */
 #ifndef RFEC_HOST_INTERNAL_H
 #define RFEC_HOST_INTERNAL_H
@@ -25,7 +26,6 @@ int check_plan(const rfec_plan* p, uint32_t max_k);
 int check_geometry(uint32_t groups, uint32_t stride, uint32_t capacity, uint32_t rows_per_group);
 void make_masks(const rfec_plan* p, rfec_kmask* M);
 uint32_t max_dlen(const uint16_t* dlen, uint32_t n);
-double now_us(void); /* CLOCK_MONOTONIC, microseconds */
 /* a tiny fork/join for the host gathers / scatters: fn(arg, lo, hi) over
  * [0, n) split across `threads` (RFEC_HOST_THREADS, default 8) */
 typedef void (*pf_fn)(void* arg, size_t lo, size_t hi);

@@ -79,11 +79,11 @@ int rfec_launch_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, c
                            uint32_t max_len, void* stream);
 int rfec_launch_gather_rows(uint8_t* dst, const uint8_t* src, const int32_t* map, uint32_t rows, uint32_t stride,
                             void* stream);
-/* the receiver session's device stage (rfec_rx.c rx_device): dst row r <- src row map[r] (zeros for
+/* the receiver session's device stage (rfec_rx_dev.c rx_device): dst row r <- src row map[r] (zeros for
  * map[r] < 0; `map` may be pinned host memory), and tbytes (a multiple of 16) of tables tsrc -> tdst */
 int rfec_launch_rx_stage(uint8_t* dst, const uint8_t* src, const int32_t* map, uint32_t rows, uint32_t stride,
                          void* tdst, const void* tsrc, size_t tbytes, void* stream);
-/* The receiver session's batch split, per parsed record (rfec_rx.c rx_phase0): its shard (fec_id % T, a
+/* The receiver session's batch split, per parsed record (rfec_rx_plane.c rx_phase0): its shard (fec_id % T, a
  * segment outside FEC by packet id; 0xFF: no effect on the control plane), its kind (RX_SPLIT_*) and the
  * value the replay's max_ts rules read (a segment's timestamp, a parity's send_ts + 3000). */
 #define RX_SPLIT_NONE 0
@@ -197,6 +197,7 @@ int rfec_launch_service(rfec_svc_ctl* ctl, rfec_svc_ctl* in, const uint8_t* shar
                         uint64_t idle_ticks, uint64_t life_ticks, uint32_t groups, void* stream);
 
 __attribute__((visibility("hidden"))) int rfec_set_error(int code, const char* what);
+__attribute__((visibility("hidden"))) double now_us(void); /* rfec_host.c: CLOCK_MONOTONIC, microseconds */
 /* sets rfec_last_error() from an errno value (0: `what` alone); returns code */
 int rfec_set_error_sys(int code, const char* what, int err);
 
