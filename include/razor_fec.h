@@ -264,6 +264,54 @@ int rfec_recover_packed_out(const rfec_plan* plan, uint32_t groups, uint32_t str
                             uint8_t* out_index, void* stream);
 
 /*
+ * Packed matrix records: the same idea for the sender's full row + column
+ * plans of k = 6..16 (flex_fec_sender_num_packets' matrix: rows of COL
+ * consecutive segments, COL = 3 for k <= 9, else 4, R = ceil(k / COL) <= 4
+ * rows; the row lines first, then the COL column lines; a last row of one
+ * member has no line, so there are NR = R or R - 1 row lines), which the
+ * row-layout calls above refuse.  A segment t lies in row r = t / COL and
+ * column c = t % COL, and either line may recover it -- at once or after a
+ * cascade -- so a slot carries both.  Group g's record,
+ * rfec_packed_matrix_stride(plan, per_group) bytes (a multiple of 64) at
+ * packed + g * stride (16-byte aligned):
+ *   +0   u64 present
+ *   +8   u64 parity_present  bit l = plan line l (rows first)
+ *   +16 + e * S, e < per_group, S = RH + CH, RH = 24 + 20 (COL - 1),
+ *        CH = 24 + 20 (R - 1): the group's e-th erased segment t (index order):
+ *        row half, RH bytes: rfec_hdr meta of row line r; u16 fec_data_size
+ *          of row r; u16 0; rfec_hdr of row r's other members in index order.
+ *          All zeros when row r has no line.
+ *        column half, CH bytes: the same for line NR + c and column c's other
+ *          members in index order.
+ *        In both halves a member that was not received holds zeros (not
+ *        whatever the hdr array held: a receiver that never saw the header
+ *        writes the same bytes), as do the positions past the line's end.
+ *        All zeros where the group has fewer than e + 1 erasures.
+ *   zeros up to the stride.
+ *   (k = 10: COL 4, R 3, S = 84 + 64 = 148; 192 bytes at per_group 1, 320 at 2.)
+ * A line only ever fires for a target of rank < per_group, whose slot holds
+ * the line's meta, size and received members; members recovered earlier in a
+ * cascade come from the earlier step: the records carry the exact peel's whole
+ * input, rejected lines and their rescheduling included.
+ * rfec_pack_erasures_matrix builds the records from the batch layout (every
+ * byte of every record is written); rfec_recover_packed_matrix_out gives
+ * rfec_recover_batch_out's out_shards, out_hdr, out_index and recovered for
+ * the batch the records describe, with no workspace (payload bytes over
+ * [0, ceil(capacity / 16) * 16) of every slot whose out_index is not 0xFF; the
+ * bytes of an unrecovered slot are unspecified).  rfec_packed_matrix_stride
+ * returns 0, and the two calls RFEC_EINVAL, for any other plan or a per_group
+ * outside [1, k].
+ */
+size_t rfec_packed_matrix_stride(const rfec_plan* plan, uint32_t per_group);
+int rfec_pack_erasures_matrix(const rfec_plan* plan, uint32_t groups, const rfec_hdr* hdr, const uint64_t* present,
+                              const rfec_hdr* meta, const uint16_t* fec_size, const uint64_t* parity_present,
+                              uint32_t per_group, uint8_t* packed, void* stream);
+int rfec_recover_packed_matrix_out(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                   const uint8_t* shards, const uint8_t* parity, const uint8_t* packed,
+                                   uint64_t* recovered, uint32_t per_group, uint8_t* out_shards, rfec_hdr* out_hdr,
+                                   uint8_t* out_index, void* stream);
+
+/*
  * Host-resident batch: the path that starts and ends in host memory (segments
  * built from UDP socket buffers, sim_session.c).  Gathers G groups of
  * sim_segment_t (segs[g*k + i], this library's SIM_VIDEO_SIZE layout) into a

@@ -14,7 +14,8 @@
  * The rest of the host layer, by concern: rfec_dropin.c (the drop-in
  * flex_fec_generate / flex_fec_recover and the resident service),
  * rfec_hostmem.c (host-memory batches), rfec_sender.c (sender staging),
- * rfec_rx_*.c (receiver ingestion and sessions).
+ * rfec_rx_*.c (receiver ingestion and sessions), rfec_packed_matrix.c (the
+ * packed records of the row + column plans).
  */
 #define _POSIX_C_SOURCE 200809L
 #ifndef __HIP_PLATFORM_AMD__

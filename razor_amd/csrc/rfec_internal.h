@@ -65,6 +65,17 @@ int rfec_launch_recover_packed(const rfec_kmask* M, uint32_t col, uint32_t group
                                uint32_t capacity, const uint8_t* shards, const uint8_t* parity, const uint8_t* packed,
                                uint32_t pk_stride, uint32_t pk_slot, uint64_t* recovered,
                                const rfec_dense_out* out, void* stream);
+/* packed matrix records (rfec_pack_erasures_matrix / rfec_recover_packed_matrix_out, rfec_packed_matrix.c): the
+ * sender's full row + column plans of k = 6..16, the shapes k_decode_matrix_dense is compiled for.
+ * rfec_packed_matrix_col: the plan's row width (3 for k <= 9, else 4), 0 for any other plan. */
+int rfec_packed_matrix_col(const rfec_kplan* P);
+int rfec_launch_pack_matrix(const rfec_kplan* P, uint32_t groups, const rfec_hdr* hdr, const uint64_t* present,
+                            const rfec_hdr* meta, const uint16_t* fsize, const uint64_t* parity_present,
+                            uint32_t per_group, uint8_t* packed, uint32_t pk_stride, void* stream);
+int rfec_launch_recover_packed_matrix(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                      const uint8_t* shards, const uint8_t* parity, const uint8_t* packed,
+                                      uint32_t pk_stride, uint64_t* recovered, const rfec_dense_out* out,
+                                      void* stream);
 int rfec_launch_wire_frame_fec(uint32_t count, uint32_t stride, uint32_t capacity, const uint8_t* parity,
                                const rfec_hdr* meta, const uint16_t* fec_size, const int8_t* status,
                                const rfec_fec_stamp* stamps, const uint32_t* order, uint32_t dstride,

@@ -894,6 +894,29 @@ __device__ __forceinline__ uint32_t cs_slot(uint32_t E, uint64_t erased, uint32_
     return E ? (uint32_t)__popcll(erased & ((1ull << i) - 1ull)) : i;
 }
 
+// Where a checker reads a group's masks and a step's header bytes (step =
+// line l recovering target t): the batch layout's five arrays (BatchHdrs), or
+// the packed matrix records (PackedMatHdrs below: the half of the target's
+// slot that belongs to the line, one contiguous run).
+struct BatchHdrs {
+    const CascArgs& A;
+    const rfec_kplan& P;
+    struct Step {
+        const uint32_t *gm, *gh;
+        const uint16_t* gf;
+        __device__ const uint32_t* meta() const { return gm; }                          // the line's fec_meta
+        __device__ uint32_t size() const { return *gf; }                                // its fec_data_size
+        __device__ const uint32_t* member(uint32_t, uint32_t i) const { return gh + i * 5; } // its u-th member, segment i
+    };
+    __device__ uint64_t present(uint32_t g) const { return A.present[2 * g]; }
+    __device__ uint64_t parity_present(uint32_t g) const { return A.parity_present[g]; }
+    __device__ Step step(uint32_t g, uint32_t l, uint32_t /* t */, uint64_t /* erased */) const
+    {
+        const uint32_t K = P.k, NL = P.n_lines;
+        return Step{A.meta_dw + (size_t)g * NL * 5 + l * 5, A.hdr_dw + (size_t)g * K * 5, A.fsize + (size_t)g * NL + l};
+    }
+};
+
 // The serial exact peel of group g (rare path: a header check failed): its
 // header records, recovered mask and out_index written; returns the schedule.
 // A step's record goes straight to its output (dense: out_hdr[g][rank], in
@@ -901,18 +924,16 @@ __device__ __forceinline__ uint32_t cs_slot(uint32_t E, uint64_t erased, uint32_
 // lane, same address, in order).  A line that fails its checks is left out and
 // the schedule recomputed -- it would fail every time it fires (same target,
 // same members, same headers), so the exact peel is the mask peel without it.
-__device__ CSched cascade_check(const CascArgs& A, const rfec_kmask& M, uint32_t g)
+template <class Hdrs>
+__device__ CSched cascade_check(const CascArgs& A, const rfec_kmask& M, const Hdrs& HS, uint32_t g)
 {
     const rfec_kplan& P = M.plan;
     const uint32_t* lines = reinterpret_cast<const uint32_t*>(P.line);
     const uint32_t K = P.k, NL = P.n_lines;
     const uint64_t kmask = K >= 64 ? ~0ull : (1ull << K) - 1ull;
-    const uint64_t have = A.present[2 * g] & kmask;
+    const uint64_t have = HS.present(g) & kmask;
     const uint64_t erased = ~have & kmask;
-    const uint64_t ppm = A.parity_present[g];
-    const uint32_t* gh = A.hdr_dw + (size_t)g * K * 5;
-    const uint32_t* gm = A.meta_dw + (size_t)g * NL * 5;
-    const uint16_t* gf = A.fsize + (size_t)g * NL;
+    const uint64_t ppm = HS.parity_present(g);
     uint32_t* const ob = A.E ? A.out_hdr_dw + (size_t)g * A.E * 5 : A.hdr_dw + (size_t)g * K * 5;
     uint32_t banned = 0;
     CSched S;
@@ -924,11 +945,12 @@ __device__ CSched cascade_check(const CascArgs& A, const rfec_kmask& M, uint32_t
         for (uint32_t s = 0; s < S.n; ++s) {
             const uint32_t l = cs_line(S, s), t = cs_tg(S, s), ln = lines[l];
             const uint32_t first = ln & 0xff, stride = (ln >> 8) & 0xff, count = (ln >> 16) & 0xff;
-            const uint32_t L = gf[l];
+            const auto st = HS.step(g, l, t, erased);
+            const uint32_t L = st.size();
             uint32_t rec[5], mem[4][5];
 #pragma unroll
             for (int d = 0; d < 5; ++d)
-                rec[d] = gm[l * 5 + d];
+                rec[d] = st.meta()[d];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const uint32_t i = first + u * stride;
@@ -936,7 +958,7 @@ __device__ CSched cascade_check(const CascArgs& A, const rfec_kmask& M, uint32_t
                 for (int d = 0; d < 5; ++d)
                     mem[u][d] = 0;
                 if ((uint32_t)u < count && i != t) {
-                    const uint32_t* r = ((erased >> i) & 1ull) ? ob + cs_slot(A.E, erased, i) * 5 : gh + i * 5;
+                    const uint32_t* r = ((erased >> i) & 1ull) ? ob + cs_slot(A.E, erased, i) * 5 : st.member(u, i);
 #pragma unroll
                     for (int d = 0; d < 5; ++d)
                         mem[u][d] = r[d];
@@ -1040,31 +1062,30 @@ __device__ __forceinline__ CSched cs_unpack(const v4u r)
 // the group's header records, recovered mask and out_index, returns its
 // schedule packed.  A group of more than LPG steps (more than LPG erasures
 // recovered) takes the serial exact peel.  Dead lanes (live false) join the
-// shuffles only.
-template <typename MT, int LPG, bool kTasks, class Lines>
-__device__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const Lines& LL, uint32_t g, bool live,
-                                   uint32_t s, uint32_t base)
+// shuffles only.  HS: where the masks and the steps' header bytes come from.
+template <typename MT, int LPG, bool kTasks, class Lines, class Hdrs>
+__device__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const Lines& LL, const Hdrs& HS, uint32_t g,
+                                   bool live, uint32_t s, uint32_t base)
 {
     const uint32_t gg = live ? g : 0u;
     const rfec_kplan& P = M.plan;
     const uint32_t K = P.k, NL = P.n_lines;
     const MT kmask = K >= 8 * sizeof(MT) ? ~MT(0) : (MT(1) << K) - MT(1);
-    const MT have = (MT)A.present[2 * gg] & kmask;
+    const MT have = (MT)HS.present(gg) & kmask;
     const MT erased = ~have & kmask;
-    const uint64_t ppm = A.parity_present[gg];
+    const uint64_t ppm = HS.parity_present(gg);
     const CSched S = cascade_schedule<MT>(LL, LL.nl(NL), have, ppm, 0u, erased, A.E);
     const bool on = live && s < S.n;
     const uint32_t l = on ? cs_line(S, s) : 0u, t = cs_tg(S, s);
     const uint32_t ln = LL.rec(l);
     const uint32_t first = ln & 0xff, stride = (ln >> 8) & 0xff, count = (ln >> 16) & 0xff;
-    const uint32_t* gh = A.hdr_dw + (size_t)gg * K * 5;
-    const uint32_t* gm = A.meta_dw + (size_t)gg * NL * 5;
+    const auto st = HS.step(gg, l, t, (uint64_t)erased);
     uint32_t L = 0, rec[5] = {0, 0, 0, 0, 0}, mem[4][5];
     if (on) {
-        L = A.fsize[(size_t)gg * NL + l];
+        L = st.size();
 #pragma unroll
         for (int d = 0; d < 5; ++d)
-            rec[d] = gm[l * 5 + d];
+            rec[d] = st.meta()[d];
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -1075,7 +1096,7 @@ __device__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const
         if (on && (uint32_t)u < count && i != t && ((erased >> i) & MT(1)) == 0) {
 #pragma unroll
             for (int d = 0; d < 5; ++d)
-                mem[u][d] = gh[i * 5 + d];
+                mem[u][d] = st.member(u, i)[d];
         }
     }
     bool ok = L <= A.capacity;
@@ -1115,7 +1136,7 @@ __device__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const
     if (!all) { // rare: a rejection -- the serial exact peel (it writes the header records)
         if (s != 0)
             return v4u{0, 0, 0, 0};
-        X = cascade_check(A, M, g);
+        X = cascade_check(A, M, HS, g);
     } else if (on) { // the recovered header record (flex_fec_xor.c:64-85)
         uint32_t* oh = (A.E ? A.out_hdr_dw + (size_t)g * A.E * 5 : A.hdr_dw + (size_t)g * K * 5) +
                        cs_slot(A.E, (uint64_t)erased, t) * 5;
@@ -1158,6 +1179,14 @@ __device__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const
         }
     }
     return cs_pack(X);
+}
+
+// (the batch layout's header arrays)
+template <typename MT, int LPG, bool kTasks, class Lines>
+__device__ __forceinline__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const Lines& LL, uint32_t g,
+                                                   bool live, uint32_t s, uint32_t base)
+{
+    return cascade_check_lanes<MT, LPG, kTasks>(A, M, LL, BatchHdrs{A, M.plan}, g, live, s, base);
 }
 
 // The checker kernel: LPG = 4 lanes per group (16 groups per wave: the
@@ -1419,22 +1448,24 @@ struct MatLines {
     __device__ uint32_t nl(uint32_t) const { return NR + COL; }
 };
 
-template <int K, int COL>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_matrix_dense(
-    CascArgs A, rfec_kmask M, uint32_t n_hr, uint32_t every, uint32_t npay8)
+// The kernel's two halves, shared with the packed-record sibling below (HS:
+// where the masks and the checker's header bytes come from).
+template <int K, int COL, class Hdrs>
+__device__ __forceinline__ void matrix_check_block(const CascArgs& A, const rfec_kmask& M, const Hdrs& HS, uint32_t hb)
+{
+    const uint32_t gt = hb * kBlock + threadIdx.x;
+    const uint32_t g = gt / kCheckLanes, s = gt % kCheckLanes;
+    const bool live = g < A.groups;
+    cascade_check_lanes<uint32_t, kCheckLanes, false>(A, M, MatLines<K, COL>{}, HS, live ? g : 0u, live, s,
+                                                      (threadIdx.x & (kWave - 1)) & ~(uint32_t)(kCheckLanes - 1));
+}
+
+template <int K, int COL, class Hdrs>
+__device__ __forceinline__ void matrix_payload_block(const CascArgs& A, const Hdrs& HS, uint32_t pb)
 {
     using LL = MatLines<K, COL>;
     constexpr int NR = LL::NR, NL = NR + COL, R = MatrixShape<K, COL>::R, MX = COL > R ? COL : R;
     static_assert(K >= 2 * COL && K <= 16 && NL <= 8 && MX <= 4, "the cascade kernels' shapes");
-    uint32_t hb = 0, pb = 0;
-    if (header_block_xcd(n_hr, every, npay8, &hb, &pb)) { // the checker blocks, as the generic kernel's
-        const uint32_t gt = hb * kBlock + threadIdx.x;
-        const uint32_t g = gt / kCheckLanes, s = gt % kCheckLanes;
-        const bool live = g < A.groups;
-        cascade_check_lanes<uint32_t, kCheckLanes, false>(A, M, LL{}, live ? g : 0u, live, s,
-                                                          (threadIdx.x & (kWave - 1)) & ~(uint32_t)(kCheckLanes - 1));
-        return;
-    }
     const uint32_t t = pb * kBlock + threadIdx.x; // (XCD-swizzled: a group's lanes share one L2)
     if (t >= A.total)
         return;
@@ -1443,8 +1474,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const uint32_t q = fdiv(rem, A.divC);
     const uint32_t j = rem - q * A.divC.d;
     const uint32_t C = A.C;
-    const uint32_t hv = (uint32_t)A.present[2 * g] & LL::KM, er = ~hv & LL::KM;
-    const uint32_t pp = (uint32_t)A.parity_present[g];
+    const uint32_t hv = (uint32_t)HS.present(g) & LL::KM, er = ~hv & LL::KM;
+    const uint32_t pp = (uint32_t)HS.parity_present(g);
     uint32_t e = er; // slot q: the q-th erased segment
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -1484,6 +1515,140 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         return;
     }
     cascade_dense_tail<uint32_t>(A, LL{}, NL, hv, er, pp, tgt, grp, par, slot0, dst, LL{});
+}
+
+template <int K, int COL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_matrix_dense(
+    CascArgs A, rfec_kmask M, uint32_t n_hr, uint32_t every, uint32_t npay8)
+{
+    const BatchHdrs HS{A, M.plan};
+    uint32_t hb = 0, pb = 0;
+    if (header_block_xcd(n_hr, every, npay8, &hb, &pb)) // the checker blocks, as the generic kernel's
+        matrix_check_block<K, COL>(A, M, HS, hb);
+    else
+        matrix_payload_block<K, COL>(A, HS, pb);
+}
+
+// The same decode from packed matrix records (rfec_recover_packed_matrix_out;
+// layout in razor_fec.h): group g's record holds its two masks, then per
+// output slot e (the group's e-th erased segment t, in row r and column c) a
+// row half -- row r's fec_meta, fec_data_size and other members' records --
+// and a column half of the same form.  A step (line l, target t) of the
+// checker reads the half of slot rank(t) that belongs to l: one contiguous
+// run where the batch layout costs a fec_data_size, a meta record and up to
+// three member records from three arrays, in sectors shared with the lines
+// that do not fire.  An erased member's position holds zeros (the checker does
+// not load it; the cascade's earlier steps supply it).  The payload lanes
+// read the record's first 16 bytes and no other header byte.
+template <int K, int COL>
+struct PackedMatHdrs {
+    static constexpr uint32_t NR = MatLines<K, COL>::NR, R = MatrixShape<K, COL>::R;
+    static constexpr uint32_t RH = 24 + 20 * (COL - 1), CH = 24 + 20 * (R - 1), S = RH + CH; // bytes
+    const uint8_t* packed;
+    uint32_t pk_stride;
+    struct Step {
+        const uint32_t* hs; // the half slot: meta (5 dwords), fec_data_size, the line's other members
+        uint32_t t;
+        __device__ const uint32_t* meta() const { return hs; }
+        __device__ uint32_t size() const { return hs[5] & 0xFFFFu; }
+        // the line's u-th member, segment i != t: the members after the target sit one position lower
+        __device__ const uint32_t* member(uint32_t u, uint32_t i) const { return hs + 6 + 5 * (u - (i > t ? 1u : 0u)); }
+    };
+    __device__ const uint64_t* rec(uint32_t g) const
+    {
+        return reinterpret_cast<const uint64_t*>(packed + (size_t)g * pk_stride);
+    }
+    __device__ uint64_t present(uint32_t g) const { return rec(g)[0]; }
+    __device__ uint64_t parity_present(uint32_t g) const { return rec(g)[1]; }
+    __device__ Step step(uint32_t g, uint32_t l, uint32_t t, uint64_t erased) const
+    {
+        const uint32_t e = (uint32_t)__popcll(erased & ((1ull << t) - 1ull)); // < per_group: the schedule's targets
+        return Step{reinterpret_cast<const uint32_t*>(packed + (size_t)g * pk_stride + 16 + e * S + (l < NR ? 0u : RH)), t};
+    }
+};
+
+template <int K, int COL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_matrix_packed(
+    CascArgs A, rfec_kmask M, uint32_t n_hr, uint32_t every, uint32_t npay8, const uint8_t* __restrict__ packed,
+    uint32_t pk_stride)
+{
+    const PackedMatHdrs<K, COL> HS{packed, pk_stride};
+    uint32_t hb = 0, pb = 0;
+    if (header_block_xcd(n_hr, every, npay8, &hb, &pb))
+        matrix_check_block<K, COL>(A, M, HS, hb);
+    else
+        matrix_payload_block<K, COL>(A, HS, pb);
+}
+
+// The batch layout -> packed matrix records (rfec_pack_erasures_matrix): one
+// lane per (group, 16-byte chunk of the record), so every byte of a record --
+// masks, slots, zeros and padding -- leaves in whole 16-byte stores (slots
+// start on 4-byte boundaries only: lanes per slot could store dwords at best).
+// A dword of slot e belongs to the row half or the column half of the group's
+// e-th erased segment t: the line's meta record, its fec_data_size, or the
+// record of one of its other members (zeros for an erased member, past the
+// line's end, for a row without a line and where the group has no e-th erased
+// segment).
+struct PackMatArgs {
+    const uint32_t* hdr;
+    const uint64_t* present;
+    const uint32_t* meta;
+    const uint16_t* fsize;
+    const uint64_t* parity_present;
+    uint32_t groups, K, COL, NR, E, RHd, Sd; // RHd, Sd: dwords of a row half and of a slot
+    uint32_t total;                          // groups x chunks per record
+    FastDiv divChunks;
+};
+
+__device__ __forceinline__ uint32_t pack_matrix_dword(const PackMatArgs& P, uint32_t g, uint64_t h, uint32_t w)
+{
+    const uint32_t e = w / P.Sd;
+    if (e >= P.E)
+        return 0; // padding
+    uint32_t m = ~(uint32_t)h & ((1u << P.K) - 1u);
+    for (uint32_t u = 0; u < e; ++u)
+        m &= m - 1u;
+    if (!m)
+        return 0;
+    const uint32_t t = (uint32_t)__ffs((int)m) - 1, r = t / P.COL, c = t - r * P.COL;
+    uint32_t x = w - e * P.Sd, l, first, stride, count;
+    if (x < P.RHd) {
+        if (r >= P.NR)
+            return 0; // a last row of one member has no line
+        l = r, first = r * P.COL, stride = 1, count = min(P.COL, P.K - first);
+    } else {
+        x -= P.RHd;
+        l = P.NR + c, first = c, stride = P.COL, count = (P.K - c + P.COL - 1) / P.COL;
+    }
+    const size_t gl = (size_t)g * (P.NR + P.COL) + l;
+    if (x < 5)
+        return P.meta[gl * 5 + x];
+    if (x == 5)
+        return P.fsize[gl];
+    const uint32_t pos = (x - 6) / 5, d = x - 6 - pos * 5, ut = (t - first) / stride;
+    const uint32_t u = pos < ut ? pos : pos + 1, i = first + u * stride;
+    if (u >= count || !((h >> i) & 1ull))
+        return 0;
+    return P.hdr[((size_t)g * P.K + i) * 5 + d];
+}
+
+__global__ __launch_bounds__(kBlock) void k_pack_matrix(v4u* __restrict__ packed, PackMatArgs P)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= P.total)
+        return;
+    const uint32_t g = fdiv(t, P.divChunks), ch = t - g * P.divChunks.d;
+    const uint64_t h = P.present[2 * g];
+    v4u v;
+    if (ch == 0) {
+        const uint64_t pp = P.parity_present[g];
+        v = v4u{(uint32_t)h, (uint32_t)(h >> 32), (uint32_t)pp, (uint32_t)(pp >> 32)};
+    } else {
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            v[d] = pack_matrix_dword(P, g, h, ch * 4 - 4 + d);
+    }
+    packed[t] = v; // record g, chunk ch: the records are contiguous
 }
 
 // ---------------------------------------------------------------------------
@@ -2673,6 +2838,70 @@ int rfec_launch_recover_packed(const rfec_kmask* M, uint32_t col, uint32_t group
         launch_packed_rows<32, 4>(F, B, *M, cd, col);
     else
         launch_packed_rows<0, 4>(F, B, *M, cd, col);
+    return (int)hipGetLastError();
+}
+
+int rfec_packed_matrix_col(const rfec_kplan* P)
+{
+    const uint32_t k = P->k, col = k <= 9 ? 3u : 4u;
+    return k >= 6 && k <= 16 && is_full_matrix(P, col) ? (int)col : 0;
+}
+
+int rfec_launch_pack_matrix(const rfec_kplan* P, uint32_t groups, const rfec_hdr* hdr, const uint64_t* present,
+                            const rfec_hdr* meta, const uint16_t* fsize, const uint64_t* parity_present,
+                            uint32_t per_group, uint8_t* packed, uint32_t pk_stride, void* stream)
+{
+    const uint32_t col = (uint32_t)rfec_packed_matrix_col(P);
+    if (!col || pk_stride % 16)
+        return (int)hipErrorInvalidValue;
+    const uint32_t R = (P->k + col - 1) / col, NR = P->n_lines - col;
+    PackMatArgs A = {reinterpret_cast<const uint32_t*>(hdr), present, reinterpret_cast<const uint32_t*>(meta), fsize,
+                     parity_present, groups, P->k, col, NR, per_group, 6u + 5u * (col - 1u),
+                     12u + 5u * (col - 1u) + 5u * (R - 1u), groups * (pk_stride / 16), // < 2^32: host-checked
+                     make_fastdiv(pk_stride / 16)};
+    RFEC_LAUNCH(k_pack_matrix, dim3(blocks_for(A.total)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+                reinterpret_cast<v4u*>(packed), A);
+    return (int)hipGetLastError();
+}
+
+int rfec_launch_recover_packed_matrix(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                      const uint8_t* shards, const uint8_t* parity, const uint8_t* packed,
+                                      uint32_t pk_stride, uint64_t* recovered, const rfec_dense_out* out, void* stream)
+{
+    if (!rfec_packed_matrix_col(&M->plan))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t cd = capacity ? (capacity + 15) / 16 : 1;
+    CascArgs A = {}; // (no header arrays, no workspace: the records carry the checker's input)
+    A.shards = const_cast<v4u*>(reinterpret_cast<const v4u*>(shards));
+    A.parity = reinterpret_cast<const v4u*>(parity);
+    A.recovered = recovered;
+    A.out_sh = reinterpret_cast<v4u*>(out->shards);
+    A.out_hdr_dw = reinterpret_cast<uint32_t*>(out->hdr);
+    A.out_index = out->index;
+    A.E = A.Q = out->per_group;
+    A.C = stride / 16;
+    A.capacity = capacity;
+    A.groups = groups;
+    A.total = groups * A.Q * cd; // < 2^32: host-checked
+    A.divC = make_fastdiv(cd);
+    A.divQC = make_fastdiv(A.Q * cd);
+    // the grid of launch_cascade's dense decode: rounds of 8 checker blocks spread over the payload's
+    const uint32_t n_hr = (blocks_for((uint64_t)groups * kCheckLanes) + 7u) >> 3;
+    const uint32_t npay8 = (blocks_for(A.total) + 7u) & ~7u;
+    const uint32_t every = n_hr ? (npay8 >> 3) / n_hr : 0u;
+    const dim3 grid(8u * n_hr + npay8);
+#define RFEC_MP(KK, CC)                                                                                           \
+    case KK:                                                                                                      \
+        RFEC_LAUNCH((k_decode_matrix_packed<KK, CC>), grid, dim3(kBlock), 0, st, A, *M, n_hr, every, npay8, packed, \
+                    pk_stride);                                                                                   \
+        break;
+    switch (M->plan.k) {
+        RFEC_MP(6, 3) RFEC_MP(7, 3) RFEC_MP(8, 3) RFEC_MP(9, 3) RFEC_MP(10, 4) RFEC_MP(11, 4) RFEC_MP(12, 4)
+        RFEC_MP(13, 4) RFEC_MP(14, 4) RFEC_MP(15, 4) RFEC_MP(16, 4)
+    default: break;
+    }
+#undef RFEC_MP
     return (int)hipGetLastError();
 }
 
