@@ -585,6 +585,10 @@ int rfec_host_send_frames(rfec_sender_state* st, const rfec_frame* frames, uint3
         }
         (void)hipEventRecord(ev[3], sm);
         hipError_t e2 = hipStreamSynchronize(sm);
+        /* an event record / wait that failed left a chunk's gather on sg that sm never waited for: the device
+           may still be reading the caller's frames and writing the staging slots */
+        if (e != hipSuccess || rc)
+            (void)hipStreamSynchronize(t_sd.sg);
         if (!rc && (e != hipSuccess || e2 != hipSuccess))
             rc = set_err(RFEC_EDEVICE, "send frames: copy / sync", e != hipSuccess ? e : e2);
         float a = 0, b = 0, d = 0; /* h2d: the tables and the slots' arrival (overlapped with the SIM_SEG

@@ -2,6 +2,8 @@
 HBM with torch (allocator only), calls the C ABI, downloads the results."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -188,3 +190,109 @@ class GpuWire:
             self.lib.set_tuning(0)
         from razor_amd.fec import WIRE_REC_DTYPE
         return _host(d_r, WIRE_REC_DTYPE, (N,)), _host(d_p, np.uint8, (N, stride))
+
+
+class GpuAux:
+    """The helper kernels' launch shims (rfec_launch_*, razor_amd/csrc/rfec_internal.h) on numpy inputs: the
+    engine of aux_kernel_cases.py.  pinned: rx_stage reads its map and its table source from rfec_pinned_alloc
+    memory, as the receiver session passes them, instead of device memory."""
+
+    def __init__(self, video_size=1200, device="cuda:0", pinned=False):
+        import aux_kernel_cases as ac
+        self.ac = ac
+        self.lib = native(video_size)
+        self.c = ac.bind_launches(self.lib.lib)
+        # the runtime the library itself is linked to (found through its handle: one runtime per process)
+        self.c.hipHostGetDevicePointer.restype = C.c_int
+        self.c.hipHostGetDevicePointer.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint]
+        self.device = torch.device(device)
+        self.pinned = pinned
+
+    def _canary(self, nbytes):
+        return torch.full((nbytes,), self.ac.CANARY, dtype=torch.uint8, device=self.device)
+
+    def _run(self, fn, *args):
+        rc = fn(*args, torch.cuda.current_stream(self.device).cuda_stream)
+        assert rc == 0, (fn.__name__, rc)
+        torch.cuda.synchronize(self.device)
+
+    def _pinned(self, a):
+        """`a` in an rfec_pinned_alloc block: (the block's keeper, the address the device reads it at -- the
+        block's device pointer, from which rfec_pinned_alloc registers the offset the library adds)."""
+        a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        arr, keep = self.lib.pinned_array((max(len(a), 16),), np.uint8)
+        arr[:len(a)] = a
+        d = C.c_void_p()
+        assert self.c.hipHostGetDevicePointer(C.byref(d), arr.ctypes.data, 0) == 0 and d.value
+        return keep, d.value
+
+    def rx_split(self, recs, T):
+        n = len(recs)
+        d_r = _dev(recs, self.device)
+        d_o = self._canary((n + self.ac.GUARD) * 8)
+        self._run(self.c.rfec_launch_rx_split, d_r.data_ptr(), n, T, d_o.data_ptr())
+        return _host(d_o, self.ac.SPLIT_DTYPE, (n + self.ac.GUARD,))
+
+    def gather_rows(self, src, map_, stride):
+        rows = len(map_)
+        d_s, d_m = _dev(src, self.device), _dev(np.ascontiguousarray(map_, np.int32), self.device)
+        d_o = self._canary((rows + self.ac.GUARD) * stride)
+        self._run(self.c.rfec_launch_gather_rows, d_o.data_ptr(), d_s.data_ptr(), d_m.data_ptr(), rows, stride)
+        return _host(d_o, np.uint8, (rows + self.ac.GUARD, stride))
+
+    def rx_stage(self, src, map_, stride, tables):
+        rows, tb = len(map_), len(tables)
+        map_ = np.ascontiguousarray(map_, np.int32)
+        d_s = _dev(src, self.device)
+        if self.pinned:
+            k_m, p_m = self._pinned(map_)
+            k_t, p_t = self._pinned(tables)
+        else:
+            k_m = torch.zeros(4, dtype=torch.uint8, device=self.device) if rows == 0 else _dev(map_, self.device)
+            k_t = torch.zeros(16, dtype=torch.uint8, device=self.device) if tb == 0 else _dev(tables, self.device)
+            p_m, p_t = k_m.data_ptr(), k_t.data_ptr()
+        d_o = self._canary((rows + self.ac.GUARD) * stride)
+        d_t = self._canary(tb + self.ac.GUARD * 16)
+        self._run(self.c.rfec_launch_rx_stage, d_o.data_ptr(), d_s.data_ptr(), p_m, rows, stride, d_t.data_ptr(), p_t,
+                  tb)
+        del k_m, k_t
+        return _host(d_o, np.uint8, (rows + self.ac.GUARD, stride)), _host(d_t, np.uint8, (tb + self.ac.GUARD * 16,))
+
+    def line_jobs(self, jobs, members, rows, outrows, stride):
+        d_j, d_m = _dev(jobs, self.device), _dev(np.ascontiguousarray(members, np.int32), self.device)
+        d_r, d_o = _dev(rows, self.device), _dev(outrows, self.device)
+        self._run(self.c.rfec_launch_line_jobs, d_j.data_ptr(), len(jobs), d_m.data_ptr(), d_r.data_ptr(),
+                  d_o.data_ptr(), stride)
+        return _host(d_o, np.uint8, outrows.shape)
+
+    def send_gather(self, blob, offsets, sizes, stride):
+        """The blob in one rfec_pinned_alloc block; src: the addresses the sender passes for such a block
+        (rfec_sender.c sd_stage: the host address + the block's device offset), 0 for a zero slot."""
+        slots = len(offsets)
+        keep, base = self._pinned(blob)
+        assert base % 16 == 0
+        src = np.where(offsets >= 0, base + offsets, 0).astype(np.uint64)
+        d_s, d_z = _dev(src, self.device), _dev(np.ascontiguousarray(sizes, np.uint16), self.device)
+        d_o = self._canary((slots + self.ac.GUARD) * stride)
+        self._run(self.c.rfec_launch_send_gather, d_s.data_ptr(), d_z.data_ptr(), slots, stride, d_o.data_ptr())
+        del keep
+        return _host(d_o, np.uint8, (slots + self.ac.GUARD, stride))
+
+    def parse_split(self, dgram, dlen, stride, capacity, max_len, T, tuning=0):
+        """rfec_launch_wire_parse_split: (recs, payload, split entries + GUARD), the split buffer pre-filled
+        with 0xAB."""
+        from razor_amd.fec import WIRE_REC_DTYPE
+        N, dstride = dgram.shape
+        d_g = _dev(dgram, self.device)
+        d_l = _dev(np.ascontiguousarray(dlen, np.uint16), self.device)
+        d_r = torch.full((N * 64,), 0xEE, dtype=torch.uint8, device=self.device)
+        d_p = torch.full((N * stride,), 0xEE, dtype=torch.uint8, device=self.device)
+        d_s = torch.full(((N + self.ac.GUARD) * 8,), 0xAB, dtype=torch.uint8, device=self.device)
+        self.lib.set_tuning(tuning)
+        try:
+            self._run(self.c.rfec_launch_wire_parse_split, N, dstride, d_g.data_ptr(), d_l.data_ptr(), stride,
+                      capacity, d_r.data_ptr(), d_p.data_ptr(), max_len, d_s.data_ptr(), T)
+        finally:
+            self.lib.set_tuning(0)
+        return (_host(d_r, WIRE_REC_DTYPE, (N,)), _host(d_p, np.uint8, (N, stride)),
+                _host(d_s, self.ac.SPLIT_DTYPE, (N + self.ac.GUARD,)))

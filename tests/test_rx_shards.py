@@ -37,23 +37,17 @@ sys.path.insert(0, str(ROOT))
 from razor_amd.build import HOST_NOHIP_SRC, HOST_SRC  # noqa: E402
 
 import pyoracle as po  # noqa: E402
+from host_stub_build import build_stub_library, have_hip_headers, stub_cmd  # noqa: E402
 from rx_cases import c3_groups, c3_metas, c3_records, c3_shuffle  # noqa: E402
 
-ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 CAP = 16
 
 
 @pytest.fixture(scope="module")
 def stub(tmp_path_factory):
-    if not (ROCM / "include" / "hip" / "hip_runtime_api.h").exists():
+    if not have_hip_headers():
         pytest.skip("HIP headers not available")
-    out = tmp_path_factory.mktemp("rxshards") / "librazor_fec_rxshards.so"
-    inc = [f"-I{ROCM / 'include'}", f"-I{ROOT / 'include'}", f"-I{ROOT / 'razor_amd' / 'csrc'}"]
-    cmd = ["gcc", "-std=c99", "-O1", "-g", "-fPIC", "-shared", "-DSIM_VIDEO_SIZE=1200", "-D__HIP_PLATFORM_AMD__", *inc,
-           *(str(ROOT / "razor_amd" / "csrc" / f) for f in HOST_SRC), str(ROOT / "razor_amd" / "csrc" / "rfec_net.c"),
-           str(ROOT / "tests" / "host_stub" / "stub_hip.c"), "-o", str(out), "-lpthread", "-lm"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    out = build_stub_library(tmp_path_factory.mktemp("rxshards") / "librazor_fec_rxshards.so")
     from razor_amd.fec import Native
     return Native(1200, path=str(out))
 
@@ -265,7 +259,7 @@ def replay_cases(oracle, tmp_path_factory):
 @pytest.fixture(scope="module", params=sorted(SANITIZERS))
 def replay_exe(request, tmp_path_factory):
     runtime, flags = SANITIZERS[request.param]
-    if not (ROCM / "include" / "hip" / "hip_runtime_api.h").exists():
+    if not have_hip_headers():
         pytest.skip("HIP headers not available")
     # the runtime linked into the executable where its archive is installed (no order among preloaded
     # libraries to get right), else the shared one
@@ -275,11 +269,8 @@ def replay_exe(request, tmp_path_factory):
         pytest.skip(f"{runtime} not installed")
     flags = flags + ([f"-static-{runtime}"] if have[".a"] else [])
     exe = tmp_path_factory.mktemp("rxreplay_" + request.param) / "rx_replay"
-    inc = [f"-I{ROCM / 'include'}", f"-I{ROOT / 'include'}", f"-I{ROOT / 'razor_amd' / 'csrc'}"]
-    cmd = ["gcc", "-std=c99", "-O1", "-g", "-fno-omit-frame-pointer", *flags, "-DSIM_VIDEO_SIZE=1200",
-           "-D__HIP_PLATFORM_AMD__", *inc, *(str(ROOT / "razor_amd" / "csrc" / f) for f in HOST_SRC),
-           str(ROOT / "razor_amd" / "csrc" / "rfec_net.c"), str(ROOT / "tests" / "host_stub" / "stub_hip.c"),
-           str(ROOT / "tests" / "host_stub" / "rx_replay.c"), "-o", str(exe), "-lpthread", "-lm"]
+    cmd = stub_cmd(exe, flags=["-fno-omit-frame-pointer", *flags],
+                   extra_src=[ROOT / "tests" / "host_stub" / "rx_replay.c"])
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     return exe

@@ -137,3 +137,73 @@ def test_send_frames_split_calls_gpu(lib, oracle1000, name, zero_copy):
     scn = {s["name"]: s for s in po.stage_fixture()["scenarios"]}[name]
     n = len(scn["frames"])
     _check_scenario(lib, oracle1000, scn, [0, 1, 2, 5, n // 2, n // 2 + 1, n], zero_copy)
+
+
+def _scenario(name):
+    return {s["name"]: s for s in po.stage_fixture()["scenarios"]}[name]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("chunks,zero_copy,split", [(2, False, False), (2, True, False), (5, False, False),
+                                                     (5, True, False), (16, False, False), (16, True, False),
+                                                     (5, True, True)])
+def test_send_frames_chunked_gpu(lib, oracle1000, monkeypatch, chunks, zero_copy, split):
+    """The chunked path (RFEC_SEND_CHUNKS, read on every call): the slots of
+    'mixed' (1,013 segments) arrive in 2, 5 and 16 chunks on the second stream
+    (k_send_gather per chunk, or an H2D per chunk), each framed as it lands,
+    and the datagrams are still the reference sender's.  split: over several
+    calls at 5 chunks, the carried rows crossing chunk edges."""
+    monkeypatch.setenv("RFEC_SEND_CHUNKS", str(chunks))
+    scn = _scenario("mixed")
+    n = len(scn["frames"])
+    _check_scenario(lib, oracle1000, scn, [0, 1, 2, 5, n // 2, n // 2 + 1, n] if split else [0, n], zero_copy)
+
+
+@pytest.mark.gpu
+def test_send_frames_default_chunking_gpu(lib, oracle1000, monkeypatch):
+    """One zero-copy call of more than 8,192 slots takes the chunked path by
+    itself (n_slots / 2,048 >= 4 chunks): 950 generated frames of 8.5-11 kB,
+    mixed ftype and protection, in one pinned block.  SIM_SEG / SIM_FEC
+    datagrams and lengths == the same call from a fresh sender state in one
+    chunk (RFEC_SEND_CHUNKS=1, the path the fixtures pin to the reference),
+    and the SIM_SEG payloads the oracle parses out == the frame bytes."""
+    rng = np.random.default_rng(8192)
+    nf = 950
+    sizes = rng.integers(8500, 11001, nf)
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    blob, keep = lib.pinned_array((int(sizes.sum()) + 64,), np.uint8)
+    blob[...] = rng.integers(0, 256, len(blob), dtype=np.uint8)
+    frames = np.zeros(nf, po.FRAME)
+    frames["data"] = np.uint64(blob.ctypes.data) + offs.astype(np.uint64)
+    frames["size"] = sizes
+    frames["ftype"] = rng.integers(0, 2, nf)
+    frames["payload_type"] = 96
+    frames["protect_fraction"] = rng.choice([30, 80, 120], nf)
+    frames["now_ms"] = 1_700_000_000_000 + 33 * np.arange(nf)
+    ms = mp = 11 * nf + 256
+    out = [lib.pinned_array(sh, dt) for sh, dt in (((ms, DSTRIDE), np.uint8), ((ms,), np.uint16),
+                                                    ((mp, DSTRIDE), np.uint8), ((mp,), np.uint16))]
+    runs = {}
+    for chunks in (None, 1):
+        if chunks is None:
+            monkeypatch.delenv("RFEC_SEND_CHUNKS", raising=False)
+        else:
+            monkeypatch.setenv("RFEC_SEND_CHUNKS", str(chunks))
+        for o in out:
+            o[0][...] = 0xEE
+        got = lib.send_frames(lib.sender_init(), frames, UID, DSTRIDE, max_segs=ms, max_parities=mp,
+                              bufs=tuple(o[0] for o in out))
+        assert got[6].zero_copy == 3 and got[6].n_segs >= 8192  # zero copy, so chunked by default at this size
+        runs[chunks] = [a.copy() for a in got[:6]]
+    for a, b in zip(runs[None], runs[1]):
+        assert np.array_equal(a, b)
+    segs, _, sdg, sdl, fdg, fdl = runs[None]
+    assert len(fdg) > 0 and (fdl > 0).all()
+    recs, pay = oracle1000.parse_batch(sdg, sdl, 1008, 1000)
+    assert (recs["status"] == 0).all() and (recs["mid"] == 0x17).all()
+    assert np.array_equal(recs["data_size"], segs["data_size"])
+    at = offs[segs["frame"]] + segs["offset"]
+    col = np.arange(1008)[None, :]
+    want = np.where(col < segs["data_size"][:, None], blob[np.minimum(at[:, None] + col, len(blob) - 1)], 0)
+    assert np.array_equal(pay, want.astype(np.uint8))
+    del keep, out

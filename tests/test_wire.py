@@ -135,36 +135,8 @@ def test_wire_parse_mixed_gpu(pwire, oracle1000, capacity, stride, dstride, N):
     messages and bad message ids; slots of 1,248-1,504 bytes (wider than 1,280:
     the datagrams still fit, the quarter-wave parse reads the first 1,280),
     payload slots up to 1,280 bytes, N not a multiple of 4."""
-    rng = np.random.default_rng(capacity + stride * 3 + dstride * 7 + N)
-    frames, lens = [], []
-    for seg in (True, False):
-        data, hdr, sizes, stamps = wc.random_batch(rng, N, stride, capacity, seg=seg)
-        over = 36 if seg else 49
-        ds = max(dstride, (capacity + over + 15) // 16 * 16)
-        if seg:
-            g, gl = oracle1000.frame_seg_batch(data, hdr, stamps, capacity, ds)
-        else:
-            g, gl = oracle1000.frame_fec_batch(data, hdr, sizes, None, stamps, capacity, ds)
-        frames.append(g[:, :dstride] if ds > dstride else np.pad(g, ((0, 0), (0, dstride - ds))))
-        lens.append(np.minimum(gl, dstride).astype(np.uint16))
-    dgram = np.concatenate(frames)
-    dlen = np.concatenate(lens)
-    pick = rng.permutation(len(dgram))[:N]
-    dgram, dlen = dgram[pick].copy(), dlen[pick].copy()
+    dgram, dlen = wc.mixed_corrupt_batch(oracle1000, capacity, stride, dstride, N)
     n = len(dgram)
-    flip = rng.random(n) < 0.08  # a flipped byte inside the message
-    for i in np.nonzero(flip & (dlen > 8))[0]:
-        dgram[i, rng.integers(0, int(dlen[i]))] ^= 1 << int(rng.integers(8))
-    cut = rng.random(n) < 0.04  # cut short (the trailer then sits elsewhere: a CRC mismatch)
-    dlen[cut] = rng.integers(0, 60, int(cut.sum()))
-    over = rng.random(n) < 0.02  # longer than the slot
-    dlen[over] = dstride + 1 + rng.integers(0, 100, int(over.sum()))
-    mid = rng.random(n) < 0.03  # another message id, CRC recomputed (a control message or a bad id)
-    for i in np.nonzero(mid & (dlen >= 10) & (dlen <= dstride))[0]:
-        L = int(dlen[i])
-        dgram[i, 1] = rng.choice([0x10, 0x12, 0x1D, 0x05, 0x40])
-        crc = oracle1000.crc32(dgram[i, :L - 4].tobytes())
-        dgram[i, L - 4:L] = np.frombuffer(crc.to_bytes(4, "big"), np.uint8)
     recs, pay = pwire.parse(dgram, dlen, stride, capacity)
     orecs, opay = oracle1000.parse_batch(dgram, dlen, stride, capacity)
     bad = np.nonzero((recs.view(np.uint8).reshape(n, 64) != orecs.view(np.uint8).reshape(n, 64)).any(1))[0]

@@ -170,3 +170,50 @@ def random_batch(rng, N, stride, capacity, seg=False):
     stamps["send_ts"] = rng.integers(0, 2**16, N) if seg else stamps["send_ts"]
     stamps["transport_seq"] = rng.integers(0, 2**16, N)
     return data, hdr, sizes.astype(np.uint16), stamps
+
+
+def mixed_corrupt_batch(oracle, capacity, stride, dstride, N, zero_ids=0.0):
+    """N datagram slots mixing SIM_SEG (every header width) and SIM_FEC in
+    random order, with flipped bytes (CRC mismatches), lengths cut short or
+    past the slot, data sizes that overrun the datagram, control messages and
+    bad message ids.  zero_ids: the fraction of datagrams framed with fec_id 0
+    (segments outside FEC) and, independently, of SIM_SEG with packet id 0 --
+    random_batch draws both from their whole range, so without it next to none
+    is 0 (drawn from a generator of its own: the batch is otherwise the same).
+    Returns (dgram [N][dstride], dlen [N])."""
+    rng = np.random.default_rng(capacity + stride * 3 + dstride * 7 + N)
+    rng_ids = np.random.default_rng(N + 1)
+    frames, lens = [], []
+    for seg in (True, False):
+        data, hdr, sizes, stamps = random_batch(rng, N, stride, capacity, seg=seg)
+        if zero_ids:
+            stamps["fec_id"][rng_ids.random(N) < zero_ids] = 0
+            if seg:
+                hdr["seq"][rng_ids.random(N) < zero_ids] = 0
+        over = 36 if seg else 49
+        ds = max(dstride, (capacity + over + 15) // 16 * 16)
+        if seg:
+            g, gl = oracle.frame_seg_batch(data, hdr, stamps, capacity, ds)
+        else:
+            g, gl = oracle.frame_fec_batch(data, hdr, sizes, None, stamps, capacity, ds)
+        frames.append(g[:, :dstride] if ds > dstride else np.pad(g, ((0, 0), (0, dstride - ds))))
+        lens.append(np.minimum(gl, dstride).astype(np.uint16))
+    dgram = np.concatenate(frames)
+    dlen = np.concatenate(lens)
+    pick = rng.permutation(len(dgram))[:N]
+    dgram, dlen = dgram[pick].copy(), dlen[pick].copy()
+    n = len(dgram)
+    flip = rng.random(n) < 0.08  # a flipped byte inside the message
+    for i in np.nonzero(flip & (dlen > 8))[0]:
+        dgram[i, rng.integers(0, int(dlen[i]))] ^= 1 << int(rng.integers(8))
+    cut = rng.random(n) < 0.04  # cut short (the trailer then sits elsewhere: a CRC mismatch)
+    dlen[cut] = rng.integers(0, 60, int(cut.sum()))
+    over = rng.random(n) < 0.02  # longer than the slot
+    dlen[over] = dstride + 1 + rng.integers(0, 100, int(over.sum()))
+    mid = rng.random(n) < 0.03  # another message id, CRC recomputed (a control message or a bad id)
+    for i in np.nonzero(mid & (dlen >= 10) & (dlen <= dstride))[0]:
+        L = int(dlen[i])
+        dgram[i, 1] = rng.choice([0x10, 0x12, 0x1D, 0x05, 0x40])
+        crc = oracle.crc32(dgram[i, :L - 4].tobytes())
+        dgram[i, L - 4:L] = np.frombuffer(crc.to_bytes(4, "big"), np.uint8)
+    return dgram, dlen
