@@ -167,11 +167,39 @@ int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec
  * Device layout (G groups, k segments, n = plan->n_lines):
  *   shards  [G][k][stride] u8    payloads, bytes beyond data_size MUST be 0
  *   hdr     [G][k]         rfec_hdr
- *   parity  [G][n][stride] u8    fec_data; bytes beyond fec_data_size are 0
+ *   parity  [G][n][stride] u8    fec_data (see "Slot tails")
  *   meta    [G][n]         rfec_hdr  (fec_meta)
  *   fec_size[G][n]         u16   (fec_data_size)
  *   status  [G][n]         i8    0, or -1 where flex_fec_generate returns -1
  * stride is a multiple of 16 and >= capacity; capacity plays SIM_VIDEO_SIZE.
+ *
+ * Alignment.  The minimum alignment of every device pointer of the batched
+ * API (this call, rfec_recover_batch[_out], the packed calls), as the kernels
+ * access them; a sub-allocated arena may place each buffer at exactly this.
+ * The entry points return RFEC_EINVAL for less:
+ *   16 bytes  shards, parity, out_shards (payload chunks move as 16-byte
+ *             vectors), workspace, packed (records are read as 16-byte vectors)
+ *    8 bytes  present, parity_present, recovered (64-bit words)
+ *    4 bytes  hdr, meta, out_hdr (rfec_hdr records move as five 32-bit words;
+ *             a 16-byte aligned array is staged with wider loads, a 4-byte
+ *             aligned one with 32-bit loads, same result)
+ *    2 bytes  fec_size
+ *    1 byte   status, out_index
+ *
+ * Slot tails.  Every call works on the CD = ceil(capacity / 16) leading
+ * 16-byte chunks of a slot (CD = 1 for capacity 0) and touches no byte of any
+ * slot from 16 * CD to the stride, under every kernel selection
+ * (rfec_set_tuning).  Of a slot a call writes:
+ *   parity line        [0, fec_data_size) the XOR of the members, [fec_data_size,
+ *                      16 * CD) zero, [16 * CD, stride) not written (they keep
+ *                      what the buffer held; a reader takes fec_data_size bytes)
+ *   recovered segment  (in place, or a dense out slot whose out_index is not
+ *                      0xFF) [0, 16 * CD) the XOR of the line's parity and its
+ *                      other members over whole chunks: [0, data_size) the
+ *                      segment, [data_size, 16 * CD) zero whenever the line's
+ *                      inputs are zero beyond their sizes (parities as encoded
+ *                      here, headers as sent); [16 * CD, stride) not written
+ * The inputs' bytes from 16 * CD to the stride are not read.
  */
 int rfec_encode_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
                       const uint8_t* shards, const rfec_hdr* hdr, uint8_t* parity, rfec_hdr* meta,
@@ -192,7 +220,10 @@ int rfec_encode_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, u
  * A line recovers its single missing member only under the conditions of
  * flex_recover_row/col and flex_fec_recover (sizes within fec_data_size).
  * `recovered` is authoritative: an erased slot whose bit stays clear holds
- * unspecified bytes afterwards (the fused decode may have written it).
+ * unspecified bytes in [0, 16 * CD) afterwards (the fused decode may have
+ * written it).  A received segment (present bit set) is only read: its slot and
+ * header are byte-identical afterwards, as are present, parity, meta, fec_size
+ * and parity_present.  What a recovered slot holds: "Slot tails" above.
  */
 size_t rfec_recover_workspace_size(const rfec_plan* plan, uint32_t groups);
 int rfec_recover_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
@@ -207,7 +238,8 @@ int rfec_recover_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, 
  * flex_fec_receiver.c:142-143): the shards and headers are only read.  The
  * e-th erased segment of group g (e-th in segment-index order among the
  * segments whose present bit is clear, e < per_group) goes to
- *   out_shards [g*per_group + e][stride]   payload bytes [0, fec_data_size)
+ *   out_shards [g*per_group + e][stride]   its payload ("Slot tails" above: chunks
+ *                                          [0, 16 * CD) written, the rest kept)
  *   out_hdr    [g*per_group + e]           its recovered header record
  *   out_index  [g*per_group + e]           its segment index, or 0xFF where
  *                                          that erased segment was not recovered

@@ -209,6 +209,38 @@ int check_geometry(uint32_t groups, uint32_t stride, uint32_t capacity, uint32_t
     return RFEC_OK;
 }
 
+/* Pointer alignment (razor_fec.h, "Alignment"): payload slots, the workspace and the packed records move as
+ * 16-byte vectors; header records as 32-bit words; masks as 64-bit words; fec_data_size as 16-bit words. */
+static int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+int check_align_in(const uint8_t* shards, const rfec_hdr* hdr, const uint8_t* parity, const rfec_hdr* meta,
+                   const uint16_t* fec_size)
+{
+    if (misaligned(shards, 16) || misaligned(parity, 16))
+        return set_err(RFEC_EINVAL, "shards and parity must be 16-byte aligned", 0);
+    if (misaligned(hdr, 4) || misaligned(meta, 4))
+        return set_err(RFEC_EINVAL, "hdr and meta must be 4-byte aligned", 0);
+    if (misaligned(fec_size, 2))
+        return set_err(RFEC_EINVAL, "fec_size must be 2-byte aligned", 0);
+    return RFEC_OK;
+}
+
+int check_align_masks(const uint64_t* present, const uint64_t* parity_present, const uint64_t* recovered)
+{
+    if (misaligned(present, 8) || misaligned(parity_present, 8) || misaligned(recovered, 8))
+        return set_err(RFEC_EINVAL, "present, parity_present and recovered must be 8-byte aligned", 0);
+    return RFEC_OK;
+}
+
+int check_align_out(const uint8_t* out_shards, const rfec_hdr* out_hdr)
+{
+    if (misaligned(out_shards, 16))
+        return set_err(RFEC_EINVAL, "out_shards must be 16-byte aligned", 0);
+    if (misaligned(out_hdr, 4))
+        return set_err(RFEC_EINVAL, "out_hdr must be 4-byte aligned", 0);
+    return RFEC_OK;
+}
+
 int rfec_encode_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
                       const uint8_t* shards, const rfec_hdr* hdr, uint8_t* parity, rfec_hdr* meta,
                       uint16_t* fec_size, int8_t* status, void* stream)
@@ -222,6 +254,8 @@ int rfec_encode_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, u
         return RFEC_OK;
     if (!shards || !hdr || !parity || !meta || !fec_size)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if ((rc = check_align_in(shards, hdr, parity, meta, fec_size)))
+        return rc;
     const int e = rfec_launch_encode(plan, groups, stride, capacity, shards, hdr, parity, meta, fec_size, status,
                                      stream, g_tuning);
     return e ? set_err(RFEC_EDEVICE, "encode launch", e) : RFEC_OK;
@@ -264,6 +298,9 @@ int rfec_recover_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, 
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
     if ((uintptr_t)workspace % 16) /* schedule records are read as 16-B vectors */
         return set_err(RFEC_EINVAL, "workspace must be 16-byte aligned", 0);
+    if ((rc = check_align_in(shards, hdr, parity, meta, fec_size)) ||
+        (rc = check_align_masks(present, parity_present, recovered)))
+        return rc;
     {   /* the fused decode's header lanes: one per (group, line slot), 32-bit lane index */
         unsigned lg = 1;
         while ((1u << lg) < plan->n_lines)
@@ -301,6 +338,9 @@ int rfec_recover_batch_out(const rfec_plan* plan, uint32_t groups, uint32_t stri
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
     if ((uintptr_t)workspace % 16)
         return set_err(RFEC_EINVAL, "workspace must be 16-byte aligned", 0);
+    if ((rc = check_align_in(shards, hdr, parity, meta, fec_size)) ||
+        (rc = check_align_masks(present, parity_present, recovered)) || (rc = check_align_out(out_shards, out_hdr)))
+        return rc;
     static __thread rfec_kmask M;
     make_masks(plan, &M);
     {   /* header lanes: one per (group, line slot), 32-bit lane index */
@@ -377,6 +417,9 @@ int rfec_pack_erasures(const rfec_plan* plan, uint32_t groups, const rfec_hdr* h
         return RFEC_OK;
     if (!hdr || !present || !meta || !fec_size || !parity_present)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if ((rc = check_align_in(NULL, hdr, NULL, meta, fec_size)) ||
+        (rc = check_align_masks(present, parity_present, NULL)))
+        return rc;
     const int e = rfec_launch_pack_rows(plan, col, groups, hdr, present, meta, fec_size, parity_present, per_group,
                                         packed, (uint32_t)pks, 24u + 20u * (col - 1u), stream);
     return e ? set_err(RFEC_EDEVICE, "pack launch", e) : RFEC_OK;
@@ -401,6 +444,9 @@ int rfec_recover_packed_out(const rfec_plan* plan, uint32_t groups, uint32_t str
         return RFEC_OK;
     if (!shards || !parity || !recovered || !out_shards || !out_hdr || !out_index)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if ((rc = check_align_in(shards, NULL, parity, NULL, NULL)) || (rc = check_align_masks(NULL, NULL, recovered)) ||
+        (rc = check_align_out(out_shards, out_hdr)))
+        return rc;
     static __thread rfec_kmask M;
     make_masks(plan, &M);
     const rfec_dense_out D = {out_shards, out_hdr, out_index, per_group};

@@ -25,6 +25,11 @@ int set_err(int code, const char* what, int hip_code);
 extern unsigned g_tuning; /* rfec_set_tuning */
 int check_plan(const rfec_plan* p, uint32_t max_k);
 int check_geometry(uint32_t groups, uint32_t stride, uint32_t capacity, uint32_t rows_per_group);
+/* pointer alignment of the batched device API (razor_fec.h, "Alignment"); NULL passes: RFEC_OK or RFEC_EINVAL */
+int check_align_in(const uint8_t* shards, const rfec_hdr* hdr, const uint8_t* parity, const rfec_hdr* meta,
+                   const uint16_t* fec_size);
+int check_align_masks(const uint64_t* present, const uint64_t* parity_present, const uint64_t* recovered);
+int check_align_out(const uint8_t* out_shards, const rfec_hdr* out_hdr);
 void make_masks(const rfec_plan* p, rfec_kmask* M);
 uint32_t max_dlen(const uint16_t* dlen, uint32_t n);
 /* a tiny fork/join for the host gathers / scatters: fn(arg, lo, hi) over

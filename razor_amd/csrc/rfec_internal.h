@@ -42,6 +42,46 @@ int rfec_launch_recover_out(const rfec_kmask* M, uint32_t groups, uint32_t strid
                             const uint64_t* parity_present, uint64_t* recovered, void* ws, void* stream,
                             unsigned flags, const rfec_dense_out* out);
 
+/* The dispatch tag: which kernel the calling thread's last batched launch (the shims above and the packed ones
+ * below) took, RFEC_PATH(kind, arg).  Host-side and thread-local: one store per launch, no device code.  For
+ * tests, which assert the path a case means to exercise; not part of razor_fec.h.  arg:
+ *   ENC_ROWS          K of k_encode_out<K, 4> (10, 32)
+ *   ENC_ROWS_RT       CMAX of k_encode_out_rt<CMAX> (4, 16)
+ *   ENC_MATRIX        k of k_encode_matrix_out<k, c> (6..16)
+ *   ENC_PLAN          0 (k_encode)
+ *   DEC_ROWS          K of k_decode_rows<K, 4, ...> (0, 10, 32) | RFEC_PATH_SLOTS | RFEC_PATH_PACKED
+ *   DEC_OUT           MAXC of k_decode_out<MAXC, slots> (4, 8) | RFEC_PATH_SLOTS
+ *   DEC_FLAT          MAXC of k_decode_disjoint<MAXC> (4, 8)
+ *   CASCADE           mask bits of k_cascade_check<u32 / u64> + k_decode_cascade (32, 64)
+ *   CASCADE_DENSE     mask bits of k_decode_cascade_dense<u32 / u64> (32, 64)
+ *   MATRIX_DENSE      k of k_decode_matrix_dense<k, c> (6..16)
+ *   PEEL_FLAT         MAXC of k_peel_lds + k_recover_flat<4, 2> / <8, 1> (4, 8) | RFEC_PATH_FAST | RFEC_PATH_DENSE
+ *   PACK_ROWS / PACK_MATRIX   0 (k_pack_rows / k_pack_matrix)
+ *   MATRIX_PACKED     k of k_decode_matrix_packed<k, c> (6..16) */
+enum {
+    RFEC_PATH_NONE = 0,
+    RFEC_PATH_ENC_ROWS,
+    RFEC_PATH_ENC_ROWS_RT,
+    RFEC_PATH_ENC_MATRIX,
+    RFEC_PATH_ENC_PLAN,
+    RFEC_PATH_DEC_ROWS,
+    RFEC_PATH_DEC_OUT,
+    RFEC_PATH_DEC_FLAT,
+    RFEC_PATH_CASCADE,
+    RFEC_PATH_CASCADE_DENSE,
+    RFEC_PATH_MATRIX_DENSE,
+    RFEC_PATH_PEEL_FLAT,
+    RFEC_PATH_PACK_ROWS,
+    RFEC_PATH_PACK_MATRIX,
+    RFEC_PATH_MATRIX_PACKED
+};
+#define RFEC_PATH_SLOTS 0x40u  /* lanes per dense output slot */
+#define RFEC_PATH_PACKED 0x80u /* header input from the packed erasure records */
+#define RFEC_PATH_FAST 0x40u   /* the replay's single-level fast form (lines of <= 8 members) */
+#define RFEC_PATH_DENSE 0x80u  /* dense output */
+#define RFEC_PATH(kind, arg) ((uint32_t)(kind) | (uint32_t)(arg) << 8)
+uint32_t rfec_last_path(void);
+
 /* recover workspace, per group: the generic peel's schedule record (step
  * count, single-level flag, then a (line, target) byte pair per step), or the
  * cascade decode's 16-byte schedule record followed by one 4-byte task word

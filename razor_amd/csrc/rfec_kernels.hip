@@ -47,6 +47,8 @@
 
 static thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
 static thread_local uint32_t t_launches = 0; // launches since rfec_timing_events
+static thread_local uint32_t t_path = RFEC_PATH_NONE; // the dispatch tag (rfec_internal.h): the last launch's kernel
+#define RFEC_TAG(kind, arg) (t_path = RFEC_PATH(kind, arg))
 
 bool rfec_timing_take(hipEvent_t* start, hipEvent_t* stop)
 {
@@ -2363,6 +2365,7 @@ hipError_t launch_rows_out(const EncLaunch& a)
     constexpr uint32_t R = (K + COL - 1) / COL;
     const uint64_t total = (uint64_t)a.groups * R * a.cd; // < 2^32: checked by the caller
     const uint32_t head = enc_head(a);
+    RFEC_TAG(RFEC_PATH_ENC_ROWS, K);
     RFEC_LAUNCH((k_encode_out<K, COL>), dim3(head + enc_rounds(total)), dim3(kBlock), 0, a.stream, a.s, a.p,
                 (uint32_t)total, a.stride / 16, make_fastdiv(a.cd), make_fastdiv(R * a.cd), head, a.E, *a.P);
     return hipGetLastError();
@@ -2374,6 +2377,7 @@ hipError_t launch_rows_out_rt(const EncLaunch& a, uint32_t col)
     const uint32_t K = a.P->k, R = (K + col - 1) / col;
     const uint64_t total = (uint64_t)a.groups * R * a.cd; // < 2^32: checked by the caller
     const uint32_t head = enc_head(a);
+    RFEC_TAG(RFEC_PATH_ENC_ROWS_RT, CMAX);
     RFEC_LAUNCH((k_encode_out_rt<CMAX>), dim3(head + enc_rounds(total)), dim3(kBlock), 0, a.stream, a.s, a.p,
                 (uint32_t)total, a.stride / 16, make_fastdiv(a.cd), make_fastdiv(R * a.cd), K, col, head, a.E,
                 *a.P);
@@ -2442,12 +2446,15 @@ hipError_t launch_encode(const EncLaunch& a, unsigned flags)
     }
     const uint32_t C = a.stride / 16;
     const uint32_t total = a.groups * a.cd;
-    if (!generic && rsrc_ok && P->k >= 6 && P->k <= 16 && is_full_matrix(P, P->k <= 9 ? 3 : 4)) {
+    // (tot below is a 32-bit lane count, as the row branch's: a larger batch takes k_encode)
+    if (!generic && rsrc_ok && P->k >= 6 && P->k <= 16 && is_full_matrix(P, P->k <= 9 ? 3 : 4) &&
+        (uint64_t)a.groups * P->n_lines * a.cd < (1ull << 32)) {
         const uint32_t head = enc_head(a);
         const uint32_t nl = P->n_lines, tot = a.groups * nl * a.cd;
         const dim3 grid_o(head + enc_rounds(tot));
 #define RFEC_MX(KK, CC)                                                                                           \
     case KK:                                                                                                      \
+        RFEC_TAG(RFEC_PATH_ENC_MATRIX, KK);                                                                       \
         RFEC_LAUNCH((k_encode_matrix_out<KK, CC>), grid_o, dim3(kBlock), 0, a.stream, a.s, a.p, tot, C,          \
                     make_fastdiv(a.cd), make_fastdiv(nl * a.cd), head, a.E, *P);                                  \
         return hipGetLastError();
@@ -2458,6 +2465,7 @@ hipError_t launch_encode(const EncLaunch& a, unsigned flags)
         }
 #undef RFEC_MX
     }
+    RFEC_TAG(RFEC_PATH_ENC_PLAN, 0);
     RFEC_LAUNCH(k_encode, dim3(a.E.n_meta_blocks + blocks_for(total)), dim3(kBlock), 0, a.stream, a.s, a.p, total, C,
                 make_fastdiv(a.cd), a.E, *P);
     return hipGetLastError();
@@ -2501,6 +2509,7 @@ void launch_cascade(CascArgs A, const rfec_kmask& M, uint32_t groups, uint32_t c
         if (!generic && k >= 6 && k <= 16 && is_full_matrix(&M.plan, k <= 9 ? 3 : 4)) {
 #define RFEC_MD(KK, CC)                                                                                           \
     case KK:                                                                                                      \
+        RFEC_TAG(RFEC_PATH_MATRIX_DENSE, KK);                                                                     \
         RFEC_LAUNCH((k_decode_matrix_dense<KK, CC>), grid, dim3(kBlock), 0, st, A, M, n_hr, every, npay8);        \
         return;
             switch (k) {
@@ -2510,6 +2519,7 @@ void launch_cascade(CascArgs A, const rfec_kmask& M, uint32_t groups, uint32_t c
             }
 #undef RFEC_MD
         }
+        RFEC_TAG(RFEC_PATH_CASCADE_DENSE, M.plan.k <= 32 ? 32 : 64);
         if (M.plan.k <= 32)
             RFEC_LAUNCH(k_decode_cascade_dense<uint32_t>, grid, dim3(kBlock), 0, st, A, M, n_hr, every, npay8);
         else
@@ -2517,6 +2527,7 @@ void launch_cascade(CascArgs A, const rfec_kmask& M, uint32_t groups, uint32_t c
         return;
     }
     const dim3 gc(blocks_for((uint64_t)groups * kCheckLanes));
+    RFEC_TAG(RFEC_PATH_CASCADE, M.plan.k <= 32 ? 32 : 64);
     if (M.plan.k <= 32)
         RFEC_LAUNCH(k_cascade_check<uint32_t>, gc, dim3(kBlock), 0, st, A, M);
     else
@@ -2535,6 +2546,7 @@ void launch_fused_out(const FusedArgs& F, const PeelArgs& B, const rfec_kmask& M
     const dim3 grid(F.n_hdr + npay);
     const FastDiv dC = make_fastdiv(cd), dLC = make_fastdiv(per * cd);
     const uint32_t every = hdr_every(F, npay);
+    RFEC_TAG(RFEC_PATH_DEC_OUT, MAXC | (slots ? RFEC_PATH_SLOTS : 0u));
     if (slots)
         RFEC_LAUNCH((k_decode_out<MAXC, true>), grid, dim3(kBlock), 0, F.stream, F.shards, F.parity, total, F.C, dC,
                     dLC, F.n_hdr, every, B, M, F.D);
@@ -2558,6 +2570,7 @@ void launch_fused_rows(const FusedArgs& F, const PeelArgs& B, const rfec_kmask& 
     const dim3 grid(8u * nhr + npay8);
     const uint32_t every = nhr ? (npay8 >> 3) / nhr : 0u;
     const FastDiv dC = make_fastdiv(cd), dRC = make_fastdiv(per * cd), dCol = make_fastdiv(cc);
+    RFEC_TAG(RFEC_PATH_DEC_ROWS, K | (slots ? RFEC_PATH_SLOTS : 0u));
     if (slots)
         RFEC_LAUNCH((k_decode_rows<K, COL, true>), grid, dim3(kBlock), 0, F.stream, F.shards, F.parity, total, F.C,
                     dC, dRC, F.n_hdr, every, B, M, F.D, npay8, kk, cc, dCol);
@@ -2577,6 +2590,7 @@ void launch_packed_rows(const FusedArgs& F, const PeelArgs& B, const rfec_kmask&
     const dim3 grid(8u * nhr + npay8);
     const uint32_t every = nhr ? (npay8 >> 3) / nhr : 0u;
     const FastDiv dC = make_fastdiv(cd), dRC = make_fastdiv(F.D.E * cd), dCol = make_fastdiv(cc);
+    RFEC_TAG(RFEC_PATH_DEC_ROWS, K | RFEC_PATH_SLOTS | RFEC_PATH_PACKED);
     RFEC_LAUNCH((k_decode_rows<K, COL, true, true>), grid, dim3(kBlock), 0, F.stream, F.shards, F.parity, total, F.C,
                 dC, dRC, F.n_hdr, every, B, M, F.D, npay8, kk, cc, dCol);
 }
@@ -2585,6 +2599,7 @@ template <int MAXC>
 void launch_fused_flat(const FusedArgs& F, const PeelArgs& B, const rfec_kmask& M)
 {
     const uint32_t npay = blocks_for(F.total);
+    RFEC_TAG(RFEC_PATH_DEC_FLAT, MAXC);
     RFEC_LAUNCH((k_decode_disjoint<MAXC>), dim3(F.n_hdr + npay), dim3(kBlock), 0, F.stream, F.shards, F.parity,
                 F.total, F.C, F.f, F.n_hdr, hdr_every(F, npay), B, M, F.D);
 }
@@ -2600,6 +2615,8 @@ extern "C" int rfec_timing_events(void* start, void* stop)
 }
 
 extern "C" uint32_t rfec_timing_launches(void) { return t_launches; }
+
+extern "C" uint32_t rfec_last_path(void) { return t_path; }
 
 extern "C" {
 
@@ -2753,11 +2770,13 @@ int launch_recover(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32
         launch_cascade(A, *M, groups, cd, ws, B.rec_bytes, st, (flags & RFEC_KFLAG_MATRIX_GENERIC) != 0);
         return (int)hipGetLastError();
     }
+    const uint32_t fast = maxc <= 8 ? 1u : 0u;
+    RFEC_TAG(RFEC_PATH_PEEL_FLAT,
+             (maxc <= 4 ? 4u : 8u) | (fast ? RFEC_PATH_FAST : 0u) | (dense ? RFEC_PATH_DENSE : 0u));
     RFEC_LAUNCH(k_peel_lds, dim3(n_hdr), dim3(kBlock), 0, st, B, *M);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return (int)e;
-    const uint32_t fast = maxc <= 8 ? 1u : 0u;
     const dim3 grid(blocks_for(total));
     if (maxc <= 4)
         RFEC_LAUNCH((k_recover_flat<4, 2>), grid, dim3(kBlock), 0, st, sh, pp, B.sched, total, C, f, B.rec_bytes, fast,
@@ -2801,6 +2820,7 @@ int rfec_launch_pack_rows(const rfec_kplan* P, uint32_t col, uint32_t groups, co
     while ((1u << lg) < per_group)
         ++lg;
     const uint32_t lanes = groups << lg; // < 2^32: host-checked
+    RFEC_TAG(RFEC_PATH_PACK_ROWS, 0);
     RFEC_LAUNCH(k_pack_rows, dim3(blocks_for(lanes)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), packed,
                 reinterpret_cast<const uint32_t*>(hdr), present, reinterpret_cast<const uint32_t*>(meta), fsize,
                 parity_present, groups, P->k, col, P->n_lines, per_group, lg, pk_stride, pk_slot);
@@ -2859,6 +2879,7 @@ int rfec_launch_pack_matrix(const rfec_kplan* P, uint32_t groups, const rfec_hdr
                      parity_present, groups, P->k, col, NR, per_group, 6u + 5u * (col - 1u),
                      12u + 5u * (col - 1u) + 5u * (R - 1u), groups * (pk_stride / 16), // < 2^32: host-checked
                      make_fastdiv(pk_stride / 16)};
+    RFEC_TAG(RFEC_PATH_PACK_MATRIX, 0);
     RFEC_LAUNCH(k_pack_matrix, dim3(blocks_for(A.total)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
                 reinterpret_cast<v4u*>(packed), A);
     return (int)hipGetLastError();
@@ -2893,6 +2914,7 @@ int rfec_launch_recover_packed_matrix(const rfec_kmask* M, uint32_t groups, uint
     const dim3 grid(8u * n_hr + npay8);
 #define RFEC_MP(KK, CC)                                                                                           \
     case KK:                                                                                                      \
+        RFEC_TAG(RFEC_PATH_MATRIX_PACKED, KK);                                                                    \
         RFEC_LAUNCH((k_decode_matrix_packed<KK, CC>), grid, dim3(kBlock), 0, st, A, *M, n_hr, every, npay8, packed, \
                     pk_stride);                                                                                   \
         break;

@@ -65,6 +65,9 @@ int rfec_pack_erasures_matrix(const rfec_plan* plan, uint32_t groups, const rfec
         return RFEC_OK;
     if (!hdr || !present || !meta || !fec_size || !parity_present)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if ((rc = check_align_in(NULL, hdr, NULL, meta, fec_size)) ||
+        (rc = check_align_masks(present, parity_present, NULL)))
+        return rc;
     const int e = rfec_launch_pack_matrix(plan, groups, hdr, present, meta, fec_size, parity_present, per_group,
                                           packed, (uint32_t)pks, stream);
     return e ? set_err(RFEC_EDEVICE, "pack launch", e) : RFEC_OK;
@@ -89,6 +92,9 @@ int rfec_recover_packed_matrix_out(const rfec_plan* plan, uint32_t groups, uint3
         return RFEC_OK;
     if (!shards || !parity || !recovered || !out_shards || !out_hdr || !out_index)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if ((rc = check_align_in(shards, NULL, parity, NULL, NULL)) || (rc = check_align_masks(NULL, NULL, recovered)) ||
+        (rc = check_align_out(out_shards, out_hdr)))
+        return rc;
     static __thread rfec_kmask M; /* 1.3 KB: keep it off the stack */
     make_masks(plan, &M);
     const rfec_dense_out D = {out_shards, out_hdr, out_index, per_group};

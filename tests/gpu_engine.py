@@ -1,5 +1,7 @@
 """Runs the product (librazor_fec.so, HIP kernels) on numpy inputs: uploads to
-HBM with torch (allocator only), calls the C ABI, downloads the results."""
+HBM with torch (allocator only), calls the C ABI, downloads the results.  The
+batched API's engine (GpuEngine) keeps each call's buffers in one guarded arena
+(guarded_arena.py) and checks guards, inputs and received segments after it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,6 +9,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+import guarded_arena as ga
 from razor_amd.fec import HDR_DTYPE, native
 
 
@@ -19,92 +22,83 @@ def _host(t: torch.Tensor, dtype, shape) -> np.ndarray:
     return t.cpu().numpy().view(dtype).reshape(shape)
 
 
-class GpuEngine:
+class TorchBackend:
+    """HBM behind guarded_arena.Arena: one uint8 tensor per arena, compared on the device."""
+
+    def __init__(self, device):
+        self.device = device
+
+    def full(self, n, byte):
+        return torch.full((n,), byte, dtype=torch.uint8, device=self.device)
+
+    def address(self, mem):
+        return mem.data_ptr()
+
+    def put(self, view, a):
+        view.copy_(torch.from_numpy(a))
+
+    def fill(self, view, byte):
+        view.fill_(byte)
+
+    def asarray(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+    def clone(self, view):
+        return view.clone()
+
+    def numpy(self, view):
+        return view.cpu().numpy()
+
+    def sync(self):
+        torch.cuda.synchronize(self.device)
+
+
+class GpuEngine(ga.ArenaEngine):
+    """The batched API on numpy inputs.  Every call lays its device buffers out
+    in one guarded arena (guarded_arena.py): each between canary guards, each at
+    exactly the alignment razor_fec.h documents; after the call the guards, the
+    input-only buffers and (in place) the received segments are checked on the
+    device.  last_path: the dispatch tag of the call's last launch
+    (rfec_internal.h RFEC_PATH)."""
+
+    HDR = HDR_DTYPE
+
     def __init__(self, video_size=1000, device="cuda:0", tuning=0, random_workspace=False):
         self.lib = native(video_size)
+        self.lib.lib.rfec_last_path.restype = C.c_uint32
+        self.lib.lib.rfec_last_path.argtypes = []
         self.device = torch.device(device)
+        self.be = TorchBackend(self.device)
         self.tuning = tuning
         self.random_workspace = random_workspace  # recover workspace starts as random bytes (not zeroed)
 
-    def encode(self, plan, shards, hdr, capacity):
-        G, k, stride = shards.shape
-        n = plan.n_lines
-        d_sh = _dev(shards, self.device)
-        d_h = _dev(hdr, self.device)
-        d_p = torch.full((G * n * stride,), 0x5A, dtype=torch.uint8, device=self.device)
-        d_m = torch.full((G * n * 20,), 0x5A, dtype=torch.uint8, device=self.device)
-        d_f = torch.zeros((G * n,), dtype=torch.int16, device=self.device)
-        d_s = torch.full((G * n,), 7, dtype=torch.int8, device=self.device)
+    def _workspace_size(self, plan, G):
+        return self.lib.workspace_size(plan, G)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _tuned(self, fn, *args):
         self.lib.set_tuning(self.tuning)
         try:
-            self.lib.encode_batch(plan, G, stride, capacity, d_sh.data_ptr(), d_h.data_ptr(), d_p.data_ptr(),
-                                  d_m.data_ptr(), d_f.data_ptr(), d_s.data_ptr(),
-                                  torch.cuda.current_stream(self.device).cuda_stream)
+            fn(*args, self._stream())
+            self.last_path = int(self.lib.lib.rfec_last_path())
             torch.cuda.synchronize(self.device)
         finally:
             self.lib.set_tuning(0)
-        return (_host(d_p, np.uint8, (G, n, stride)), _host(d_m, HDR_DTYPE, (G, n)),
-                _host(d_f, np.uint16, (G, n)), _host(d_s, np.int8, (G, n)))
 
-    def recover(self, plan, shards, hdr, present, parity, meta, fsize, pp, capacity):
-        G, k, stride = shards.shape
-        d_sh = _dev(shards, self.device)
-        d_h = _dev(hdr, self.device)
-        d_pr = _dev(np.ascontiguousarray(present, np.uint64), self.device)
-        d_p = _dev(parity, self.device)
-        d_m = _dev(meta, self.device)
-        d_f = _dev(np.ascontiguousarray(fsize, np.uint16), self.device)
-        d_pp = _dev(np.ascontiguousarray(pp, np.uint64), self.device)
-        d_rec = torch.full((G * 16,), 0xEE, dtype=torch.uint8, device=self.device)
-        nws = max(16, self.lib.workspace_size(plan, G))
-        ws = (torch.randint(0, 256, (nws,), dtype=torch.uint8, device=self.device) if self.random_workspace
-              else torch.zeros((nws,), dtype=torch.uint8, device=self.device))
-        self.lib.set_tuning(self.tuning)
-        try:
-            self.lib.recover_batch(plan, G, stride, capacity, d_sh.data_ptr(), d_h.data_ptr(), d_pr.data_ptr(),
-                                   d_p.data_ptr(), d_m.data_ptr(), d_f.data_ptr(), d_pp.data_ptr(),
-                                   d_rec.data_ptr(), ws.data_ptr(),
-                                   torch.cuda.current_stream(self.device).cuda_stream)
-            torch.cuda.synchronize(self.device)
-        finally:
-            self.lib.set_tuning(0)
-        return (_host(d_sh, np.uint8, (G, k, stride)), _host(d_h, HDR_DTYPE, (G, k)),
-                _host(d_rec, np.uint64, (G, 2)))
+    def _encode(self, plan, G, stride, capacity, A):
+        self._tuned(self.lib.encode_batch, plan, G, stride, capacity, *(A.ptr(n) for n in (
+            "shards", "hdr", "parity", "meta", "fec_size", "status")))
 
-    def recover_out(self, plan, shards, hdr, present, parity, meta, fsize, pp, capacity, per_group):
-        """rfec_recover_batch_out: returns (out_shards [G][E][stride], out_hdr
-        [G][E], out_index [G][E], recovered [G][2]) and checks that the inputs
-        were left untouched."""
-        G, k, stride = shards.shape
-        E = per_group
-        d_sh = _dev(shards, self.device)
-        d_h = _dev(hdr, self.device)
-        d_pr = _dev(np.ascontiguousarray(present, np.uint64), self.device)
-        d_p = _dev(parity, self.device)
-        d_m = _dev(meta, self.device)
-        d_f = _dev(np.ascontiguousarray(fsize, np.uint16), self.device)
-        d_pp = _dev(np.ascontiguousarray(pp, np.uint64), self.device)
-        d_rec = torch.full((G * 16,), 0xEE, dtype=torch.uint8, device=self.device)
-        o_sh = torch.full((G * E * stride,), 0x3C, dtype=torch.uint8, device=self.device)
-        o_h = torch.full((G * E * 20,), 0x3C, dtype=torch.uint8, device=self.device)
-        o_i = torch.full((G * E,), 0x3C, dtype=torch.uint8, device=self.device)
-        nws = max(16, self.lib.workspace_size(plan, G))
-        ws = (torch.randint(0, 256, (nws,), dtype=torch.uint8, device=self.device) if self.random_workspace
-              else torch.zeros((nws,), dtype=torch.uint8, device=self.device))
-        self.lib.set_tuning(self.tuning)
-        try:
-            self.lib.recover_batch_out(plan, G, stride, capacity, d_sh.data_ptr(), d_h.data_ptr(), d_pr.data_ptr(),
-                                       d_p.data_ptr(), d_m.data_ptr(), d_f.data_ptr(), d_pp.data_ptr(),
-                                       d_rec.data_ptr(), E, o_sh.data_ptr(), o_h.data_ptr(), o_i.data_ptr(),
-                                       ws.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-            torch.cuda.synchronize(self.device)
-        finally:
-            self.lib.set_tuning(0)
-        assert np.array_equal(_host(d_sh, np.uint8, (G, k, stride)), shards), "shards written"
-        assert np.array_equal(_host(d_h, HDR_DTYPE, (G, k)), hdr), "headers written"
-        return (_host(o_sh, np.uint8, (G, E, stride)), _host(o_h, HDR_DTYPE, (G, E)), _host(o_i, np.uint8, (G, E)),
-                _host(d_rec, np.uint64, (G, 2)))
+    def _recover(self, plan, G, stride, capacity, A):
+        self._tuned(self.lib.recover_batch, plan, G, stride, capacity, *(A.ptr(n) for n in (
+            "shards", "hdr", "present", "parity", "meta", "fec_size", "parity_present", "recovered", "workspace")))
 
+    def _recover_out(self, plan, G, stride, capacity, E, A):
+        self._tuned(self.lib.recover_batch_out, plan, G, stride, capacity, *(A.ptr(n) for n in (
+            "shards", "hdr", "present", "parity", "meta", "fec_size", "parity_present", "recovered")), E,
+            *(A.ptr(n) for n in ("out_shards", "out_hdr", "out_index", "workspace")))
 
     def recover_packed(self, plan, shards, hdr, present, parity, meta, fsize, pp, capacity, per_group, packed=None):
         """rfec_pack_erasures (on the device, unless `packed` gives the records)
@@ -112,33 +106,37 @@ class GpuEngine:
         recovered, packed records [G][stride] as built)."""
         G, k, stride = shards.shape
         E = per_group
+        n = plan.n_lines
         pks = self.lib.packed_stride(plan, E)
         assert pks > 0
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        d_sh = _dev(shards, self.device)
-        d_p = _dev(parity, self.device)
+        B = ga.Buf
+        bufs = [B("shards", shards.size, shards, "in"), B("parity", G * n * stride, parity, "in")]
         if packed is None:
-            d_h = _dev(hdr, self.device)
-            d_pr = _dev(np.ascontiguousarray(present, np.uint64), self.device)
-            d_m = _dev(meta, self.device)
-            d_f = _dev(np.ascontiguousarray(fsize, np.uint16), self.device)
-            d_pp = _dev(np.ascontiguousarray(pp, np.uint64), self.device)
-            d_pk = torch.full((G * pks,), 0x77, dtype=torch.uint8, device=self.device)
-            self.lib.pack_erasures(plan, G, d_h.data_ptr(), d_pr.data_ptr(), d_m.data_ptr(), d_f.data_ptr(),
-                                   d_pp.data_ptr(), E, d_pk.data_ptr(), st)
+            bufs += [B("hdr", G * k * ga.HDR_BYTES, hdr, "in"),
+                     B("present", G * 16, np.ascontiguousarray(present, np.uint64), "in"),
+                     B("meta", G * n * ga.HDR_BYTES, meta, "in"),
+                     B("fec_size", G * n * 2, np.ascontiguousarray(fsize, np.uint16), "in"),
+                     B("parity_present", G * 8, np.ascontiguousarray(pp, np.uint64), "in"),
+                     B("packed", G * pks, 0x77, "out")]
         else:
             assert packed.shape == (G, pks)
-            d_pk = _dev(packed, self.device)
-        d_rec = torch.full((G * 16,), 0xEE, dtype=torch.uint8, device=self.device)
-        o_sh = torch.full((G * E * stride,), 0x3C, dtype=torch.uint8, device=self.device)
-        o_h = torch.full((G * E * 20,), 0x3C, dtype=torch.uint8, device=self.device)
-        o_i = torch.full((G * E,), 0x3C, dtype=torch.uint8, device=self.device)
-        self.lib.recover_packed_out(plan, G, stride, capacity, d_sh.data_ptr(), d_p.data_ptr(), d_pk.data_ptr(),
-                                    d_rec.data_ptr(), E, o_sh.data_ptr(), o_h.data_ptr(), o_i.data_ptr(), st)
-        torch.cuda.synchronize(self.device)
-        assert np.array_equal(_host(d_sh, np.uint8, (G, k, stride)), shards), "shards written"
-        return (_host(o_sh, np.uint8, (G, E, stride)), _host(o_h, HDR_DTYPE, (G, E)), _host(o_i, np.uint8, (G, E)),
-                _host(d_rec, np.uint64, (G, 2)), _host(d_pk, np.uint8, (G, pks)))
+            bufs += [B("packed", G * pks, packed, "in")]
+        bufs += [B("recovered", G * 16, 0xEE, "out"), B("out_shards", G * E * stride, 0x3C, "out"),
+                 B("out_hdr", G * E * ga.HDR_BYTES, 0x3C, "out"), B("out_index", G * E, 0x3C, "out")]
+        A = ga.Arena(self.be, bufs)
+        st = self._stream()
+        if packed is None:
+            self.lib.pack_erasures(plan, G, *(A.ptr(n) for n in ("hdr", "present", "meta", "fec_size",
+                                                                 "parity_present")), E, A.ptr("packed"), st)
+            self.pack_path = int(self.lib.lib.rfec_last_path())
+        self.lib.recover_packed_out(plan, G, stride, capacity, A.ptr("shards"), A.ptr("parity"), A.ptr("packed"),
+                                    A.ptr("recovered"), E, A.ptr("out_shards"), A.ptr("out_hdr"), A.ptr("out_index"),
+                                    st)
+        self.last_path = int(self.lib.lib.rfec_last_path())
+        self._finish(A, "recover_packed")
+        return (A.get("out_shards", np.uint8, (G, E, stride)), A.get("out_hdr", HDR_DTYPE, (G, E)),
+                A.get("out_index", np.uint8, (G, E)), A.get("recovered", np.uint64, (G, 2)),
+                A.get("packed", np.uint8, (G, pks)))
 
 
 class GpuWire:

@@ -87,6 +87,64 @@ def test_argument_validation(product):
         product.zero_tails(1 << 30, 8, 1200, 1, 1, None)
 
 
+def test_pointer_alignment_validation(product):
+    """razor_fec.h "Alignment": every batched entry point rejects a pointer below
+    its documented minimum with RFEC_EINVAL before any launch (all other
+    arguments valid, each pointer in turn one step below its minimum), and the
+    error names the buffer."""
+    from razor_amd.fec import RfecError
+    rows = product.plan_matrix(10, 3, 4, 1)
+    full = product.plan_matrix(10, 3, 4, 3)
+    A = 1 << 20  # any address aligned to more than 16
+    need = {"shards": 16, "parity": 16, "out_shards": 16, "workspace": 16, "packed": 16, "present": 8,
+            "parity_present": 8, "recovered": 8, "hdr": 4, "meta": 4, "out_hdr": 4, "fec_size": 2, "status": 1,
+            "out_index": 1}
+    calls = {
+        "encode": (lambda p: product.encode_batch(rows, 4, 1200, 1200, p["shards"], p["hdr"], p["parity"], p["meta"],
+                                                  p["fec_size"], p["status"]),
+                   ["shards", "hdr", "parity", "meta", "fec_size", "status"]),
+        "recover": (lambda p: product.recover_batch(rows, 4, 1200, 1200, p["shards"], p["hdr"], p["present"],
+                                                    p["parity"], p["meta"], p["fec_size"], p["parity_present"],
+                                                    p["recovered"], p["workspace"]),
+                    ["shards", "hdr", "present", "parity", "meta", "fec_size", "parity_present", "recovered",
+                     "workspace"]),
+        "recover_out": (lambda p: product.recover_batch_out(rows, 4, 1200, 1200, p["shards"], p["hdr"], p["present"],
+                                                            p["parity"], p["meta"], p["fec_size"],
+                                                            p["parity_present"], p["recovered"], 2, p["out_shards"],
+                                                            p["out_hdr"], p["out_index"], p["workspace"]),
+                        ["shards", "hdr", "present", "parity", "meta", "fec_size", "parity_present", "recovered",
+                         "out_shards", "out_hdr", "out_index", "workspace"]),
+        "pack": (lambda p: product.pack_erasures(rows, 4, p["hdr"], p["present"], p["meta"], p["fec_size"],
+                                                 p["parity_present"], 2, p["packed"]),
+                 ["hdr", "present", "meta", "fec_size", "parity_present", "packed"]),
+        "recover_packed": (lambda p: product.recover_packed_out(rows, 4, 1200, 1200, p["shards"], p["parity"],
+                                                                p["packed"], p["recovered"], 2, p["out_shards"],
+                                                                p["out_hdr"], p["out_index"]),
+                           ["shards", "parity", "packed", "recovered", "out_shards", "out_hdr", "out_index"]),
+        "pack_matrix": (lambda p: product.pack_erasures_matrix(full, 4, p["hdr"], p["present"], p["meta"],
+                                                               p["fec_size"], p["parity_present"], 2, p["packed"]),
+                        ["hdr", "present", "meta", "fec_size", "parity_present", "packed"]),
+        "recover_packed_matrix": (lambda p: product.recover_packed_matrix_out(full, 4, 1200, 1200, p["shards"],
+                                                                              p["parity"], p["packed"],
+                                                                              p["recovered"], 2, p["out_shards"],
+                                                                              p["out_hdr"], p["out_index"]),
+                                  ["shards", "parity", "packed", "recovered", "out_shards", "out_hdr", "out_index"]),
+    }
+    n = 0
+    for what, (call, names) in calls.items():
+        for bad in names:
+            if need[bad] == 1:
+                continue  # byte arrays: any address
+            ptrs = {nm: A + 4096 * i for i, nm in enumerate(names)}
+            ptrs[bad] += need[bad] // 2  # aligned to half the minimum only
+            with pytest.raises(RfecError) as e:
+                call(ptrs)
+            assert "(-1)" in str(e.value) and bad in str(e.value) and "aligned" in str(e.value), (what, bad,
+                                                                                                   str(e.value))
+            n += 1
+    assert n == 49
+
+
 def test_packed_records_geometry(product, oracle1000):
     """rfec_packed_stride and the packed entry points' checks (no launch): row
     layouts of rows <= 4 and k <= 64 only; the host packer (parity_cases) has

@@ -1183,10 +1183,12 @@ def test_dense_output_long_schedules_gpu(gpu, oracle1000, k):
 @pytest.mark.parametrize("tuning", list(TUNINGS))
 def test_row_plan_encode_gpu(gpu, oracle1000, oracle1200, k, col, S, tuning):
     """Row layouts other than the compiled k = 10 / 32 ones (strip-mode plans,
-    flex_fec_sender.c:112-132) through the run-time-k output-mapped encode
-    (rows of up to 16 members; wider rows take the plan-driven kernel):
-    parity bytes, meta records, sizes and status equal the oracle's on ragged
-    segments."""
+    flex_fec_sender.c:112-132): parity bytes, meta records, sizes and status
+    equal the oracle's on ragged segments.  The kernel that serves each shape
+    is asserted through the dispatch tag: the run-time-k output-mapped encode
+    of rows up to 4 or up to 16 members, the plan-driven kernel for wider rows
+    and under RFEC_TUNE_GENERIC."""
+    import geometry_cases as gc
     o = oracle1200 if S > 1000 else oracle1000
     rows = (k + col - 1) // col
     plan = o.plan_matrix(k, rows, col, 1)
@@ -1194,7 +1196,11 @@ def test_row_plan_encode_gpu(gpu, oracle1000, oracle1200, k, col, S, tuning):
     shards, hdr = o.fill_groups(61 + k, G, k, S, ragged=True)
     cap = min(o.video_size, S)
     e_p, e_m, e_f, e_s = o.encode_batch(plan, shards, hdr, cap)
-    p, m, f, s = gpu(tuning=TUNINGS[tuning]).encode(plan, shards, hdr, cap)
+    eng = gpu(tuning=TUNINGS[tuning])
+    p, m, f, s = eng.encode(plan, shards, hdr, cap)
+    want = (gc.tag("ENC_PLAN") if tuning == "generic" or col > 16 else
+            gc.tag("ENC_ROWS_RT", 4 if col <= 4 else 16))
+    assert eng.last_path == want, (gc.tag_name(eng.last_path), gc.tag_name(want))
     assert np.array_equal(s, e_s) and np.array_equal(f, e_f)
     ok = e_s == 0
     assert np.array_equal(m[ok], e_m[ok])

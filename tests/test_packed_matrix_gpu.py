@@ -5,6 +5,7 @@ reference receiver's erasure fixtures."""
 import numpy as np
 import pytest
 
+import geometry_cases as gc
 import packed_matrix_cases as pm
 import parity_cases as pc
 import pyoracle as po
@@ -55,6 +56,8 @@ class PackedMatrixEngine:
             d_pk = torch.full((G * pks,), 0x77, dtype=torch.uint8, device=self.device)
             self.lib.pack_erasures_matrix(plan, G, d_h.data_ptr(), d_pr.data_ptr(), d_m.data_ptr(), d_f.data_ptr(),
                                           d_pp.data_ptr(), E, d_pk.data_ptr(), st)
+            self.pack_path = int(self.lib.lib.rfec_last_path())
+            assert self.pack_path == gc.tag("PACK_MATRIX"), gc.tag_name(self.pack_path)
         else:
             assert packed.shape == (G, pks)
             d_pk = _dev(packed, self.device)
@@ -65,6 +68,8 @@ class PackedMatrixEngine:
         self.lib.recover_packed_matrix_out(plan, G, stride, capacity, d_sh.data_ptr(), d_p.data_ptr(),
                                            d_pk.data_ptr(), d_rec.data_ptr(), E, o_sh.data_ptr(), o_h.data_ptr(),
                                            o_i.data_ptr(), st)
+        self.last_path = int(self.lib.lib.rfec_last_path())  # the dispatch tag: the kernel compiled for this k
+        assert self.last_path == gc.tag("MATRIX_PACKED", plan.k), gc.tag_name(self.last_path)
         torch.cuda.synchronize(self.device)
         assert np.array_equal(_host(d_sh, np.uint8, (G, k, stride)), shards), "shards written"
         return (_host(o_sh, np.uint8, (G, E, stride)), _host(o_h, HDR_DTYPE, (G, E)), _host(o_i, np.uint8, (G, E)),
