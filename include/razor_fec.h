@@ -185,6 +185,8 @@ int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec
  *             aligned one with 32-bit loads, same result)
  *    2 bytes  fec_size
  *    1 byte   status, out_index
+ * (rfec_wire_encode_fec, the one wire-codec call that checks alignment: 16
+ * bytes shards and dgram, 4 bytes hdr, stamps and order, 2 bytes dlen)
  *
  * Slot tails.  Every call works on the CD = ceil(capacity / 16) leading
  * 16-byte chunks of a slot (CD = 1 for capacity 0) and touches no byte of any
@@ -394,7 +396,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_parse) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_parse) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -476,6 +478,32 @@ int rfec_wire_frame_fec(uint32_t count, uint32_t stride, uint32_t capacity, cons
 int rfec_wire_frame_seg(uint32_t count, uint32_t stride, uint32_t capacity, const uint8_t* shards,
                         const rfec_hdr* hdr, const rfec_seg_stamp* stamps, const uint32_t* order, uint32_t dstride,
                         uint8_t* dgram, uint16_t* dlen, void* stream);
+
+/* A batch of groups straight into its SIM_FEC datagrams, the encode and the
+ * framing in one kernel: with count = groups * plan->n_lines, dgram
+ * [count][dstride] and dlen [count] are byte for byte what
+ *   rfec_encode_batch(plan, groups, stride, capacity, shards, hdr, parity,
+ *                     meta, fec_size, status, ...), then
+ *   rfec_wire_frame_fec(count, stride, capacity, parity, meta, fec_size,
+ *                       status, stamps, order, dstride, dgram, dlen, ...)
+ * write on the same inputs (datagram g*n + l = line l of group g; a line
+ * whose flex_fec_generate would fail -- fewer than 2 members, or a member's
+ * data_size above capacity -- gets length 0 and a zero slot; `order` as for
+ * rfec_wire_frame_fec), without the parity, meta, fec_size and status arrays:
+ * every member is read once per line it sits on and nothing but the datagram
+ * slots and lengths is written ("Slot tails": the shards' bytes from 16 * CD
+ * to the stride are not read).  k <= RFEC_MAX_K_ENCODE.
+ * Alignment (RFEC_EINVAL for less): 16 bytes shards and dgram, 4 bytes hdr,
+ * stamps and order, 2 bytes dlen.
+ * Datagram slots up to 1,280 bytes only (both SIM_VIDEO_SIZEs fit: 1,000 + 49
+ * and 1,200 + 49): dstride > 1280 returns RFEC_EINVAL -- use the two calls
+ * above.  A batch of any size is taken (shards beyond 4 GiB are split over
+ * several launches); with `order`, count * dstride must stay below 4 GiB
+ * (RFEC_EINVAL).  RFEC_WIRE_ENCODE_CHUNK_GROUPS (environment, for tests) caps
+ * the groups per launch. */
+int rfec_wire_encode_fec(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                         const uint8_t* shards, const rfec_hdr* hdr, const rfec_fec_stamp* stamps,
+                         const uint32_t* order, uint32_t dstride, uint8_t* dgram, uint16_t* dlen, void* stream);
 
 /* Parse status (rfec_wire_rec.status). */
 #define RFEC_WIRE_OK 0         /* SIM_SEG / SIM_FEC decoded (a SEG with a bad data length decodes

@@ -15,7 +15,8 @@
  * flex_fec_generate / flex_fec_recover and the resident service),
  * rfec_hostmem.c (host-memory batches), rfec_sender.c (sender staging),
  * rfec_rx_*.c (receiver ingestion and sessions), rfec_packed_matrix.c (the
- * packed records of the row + column plans).
+ * packed records of the row + column plans), rfec_wire_fused.c (the encode
+ * and the SIM_FEC framing in one kernel).
  */
 #define _POSIX_C_SOURCE 200809L
 #ifndef __HIP_PLATFORM_AMD__
@@ -474,7 +475,7 @@ int rfec_zero_tails(uint32_t groups, uint32_t k, uint32_t stride, uint8_t* shard
 /* ------------------------------------------------------------------------ */
 /* 2b. wire codec (sim_proto.c / sim_proto.inl), batched                     */
 /* ------------------------------------------------------------------------ */
-static int check_wire(uint32_t count, uint32_t stride, uint32_t capacity, uint32_t dstride, uint32_t overhead)
+int check_wire(uint32_t count, uint32_t stride, uint32_t capacity, uint32_t dstride, uint32_t overhead)
 {
     if (stride == 0 || stride % 16 || stride > RFEC_WIRE_MAX_DSTRIDE)
         return set_err(RFEC_EINVAL, "stride must be a positive multiple of 16, at most 2048", 0);

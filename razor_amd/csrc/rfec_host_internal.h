@@ -2,7 +2,7 @@
  * rfec_host_internal.h -- declarations shared by the C host layer's
  * translation units that use the HIP runtime (rfec_host.c, rfec_dropin.c,
  * rfec_hostmem.c, rfec_sender.c, rfec_rx_dev.c, rfec_rx_session.c,
- * rfec_packed_matrix.c; the
+ * rfec_packed_matrix.c, rfec_wire_fused.c; the
  * receiver's host-only units rfec_rx_sim.c, rfec_rx_pool.c, rfec_rx_plane.c
  * do without it).  Internal: hidden from the shared library's exports.
  */
@@ -32,6 +32,9 @@ int check_align_masks(const uint64_t* present, const uint64_t* parity_present, c
 int check_align_out(const uint8_t* out_shards, const rfec_hdr* out_hdr);
 void make_masks(const rfec_plan* p, rfec_kmask* M);
 uint32_t max_dlen(const uint16_t* dlen, uint32_t n);
+/* the wire codec's geometry rules (razor_fec.h, wire codec): stride, capacity, dstride; overhead: the bytes a
+ * datagram adds to its payload (0: none required) */
+int check_wire(uint32_t count, uint32_t stride, uint32_t capacity, uint32_t dstride, uint32_t overhead);
 /* a tiny fork/join for the host gathers / scatters: fn(arg, lo, hi) over
  * [0, n) split across `threads` (RFEC_HOST_THREADS, default 8) */
 typedef void (*pf_fn)(void* arg, size_t lo, size_t hi);

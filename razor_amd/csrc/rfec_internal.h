@@ -123,6 +123,14 @@ int rfec_launch_wire_frame_fec(uint32_t count, uint32_t stride, uint32_t capacit
 int rfec_launch_wire_frame_seg(uint32_t count, uint32_t stride, uint32_t capacity, const uint8_t* shards,
                                const rfec_hdr* hdr, const rfec_seg_stamp* stamps, const uint32_t* order,
                                uint32_t dstride, uint8_t* dgram, uint16_t* dlen, uint32_t rows_out, void* stream);
+/* rfec_wire_encode_fec (rfec_wire_fused.c): one launch of the fused encode + SIM_FEC framing over `groups` groups,
+ * datagram g * n_lines + l -> slot order[...] (or its own index) of `dgram`, which holds rows_out slots.  The
+ * caller keeps (groups * k + 4) * stride + 1280, groups * k * 20 and rows_out * dstride below 0xFFFFFFF0
+ * (32-bit buffer offsets) and dstride <= 1280; hipErrorInvalidValue otherwise. */
+int rfec_launch_wire_encode_fec(const rfec_kplan* P, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                const uint8_t* shards, const rfec_hdr* hdr, const rfec_fec_stamp* stamps,
+                                const uint32_t* order, uint32_t dstride, uint8_t* dgram, uint16_t* dlen,
+                                uint32_t rows_out, void* stream);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */
 int rfec_launch_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const uint16_t* dlen,

@@ -1738,6 +1738,229 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
     }
 }
 
+// k_frame_fec_q's stage after its loads, for k_encode_frame_fec_q: a quad's datagram from its payload windows W
+// and its 13 field dwords F -- the header, the funnel by 3 bytes, the mask at the length, the CRC32 and its
+// trailer, the stores.  valid: the parity was generated and fits (else length 0 and a zero slot).  A copy:
+// with k_frame_fec_q calling it too, that kernel kept its 64 VGPRs, 78 SGPRs and 8 bytes of scratch but came
+// out 4 instructions longer with other registers (101.1 / 101.8 us against 102.1 / 102.9 in bench.py --full
+// of the parent and of the tree alternating, inside the +-1 us that identical code shows between runs), so
+// its body stays as it was and compiles to the same instructions as before.
+__device__ __forceinline__ void frame_fec_store_q(const uint32_t* T, const v4u (&W)[kQRows], const uint32_t (&F)[13],
+                                                  bool valid, bool act, uint32_t o, uint32_t s,
+                                                  __amdgpu_buffer_rsrc_t rout, uint16_t* __restrict__ dlen,
+                                                  uint32_t dstride)
+{
+    const uint32_t L = F[11];
+    const uint32_t n = valid ? 45u + L : 0u;
+    // header dwords 4 s .. 4 s + 3 for lanes 0-2
+    uint32_t Hd[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t h0 = fec_hdr_dword(F, j), h1 = fec_hdr_dword(F, 4 + j), h2 = fec_hdr_dword(F, 8 + j);
+        Hd[j] = s == 0 ? h0 : (s == 1 ? h1 : (s == 2 ? h2 : 0u));
+    }
+    uint32_t out[kQRows][4];
+    {
+        uint32_t nx[kQRows];
+#pragma unroll
+        for (int k = 0; k < kQRows; ++k)
+            nx[k] = dpp(W[k][0], kDppRowRor15);
+#pragma unroll
+        for (int k = 0; k < kQRows; ++k) {
+            uint32_t w[5] = {W[k][0], W[k][1], W[k][2], W[k][3],
+                             s == 15 ? (k + 1 < kQRows ? nx[k + 1 < kQRows ? k + 1 : k] : 0u) : nx[k]};
+            if (k == 0) { // lanes 0-1: header only; lane 2: payload bytes 0-2 at its end
+                const uint32_t p0 = w[0];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    w[j] = s > 2 ? w[j] : 0u;
+                w[4] = s > 2 ? w[4] : (s == 2 ? p0 : 0u);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                out[k][j] = __builtin_amdgcn_alignbyte(w[j + 1], w[j], 3);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        out[0][j] |= Hd[j];
+    mask_q(out, n, s);
+    // CRC32 (Horner over the rows, seed folded into the first dword)
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < kQRows; ++k) {
+        const uint32_t x0 = out[k][0] ^ (k == 0 && s == 0 ? ~RFEC_WIRE_CRC_SEED : 0u);
+        acc = (k ? mul_row(T, acc) : 0u) ^ slice16(T, x0, out[k][1], out[k][2], out[k][3]);
+    }
+    const uint32_t D = kQWindow - n, Dq = D >> 4, Dr = D & 15u;
+    const uint32_t R = row_xor(carry_q(T, acc, s + Dq));
+    const uint32_t* iv = T + kQInv + Dr * 32u;
+    const uint32_t b = (((R >> s) & 1u) ? iv[s] : 0u) ^ (((R >> (s + 16u)) & 1u) ? iv[s + 16u] : 0u);
+    const uint32_t crc = ~row_xor(b);
+    if (valid) { // big-endian trailer at byte n
+        const uint32_t be = bswap(crc), s4 = n & 3u, q0 = n >> 2;
+        const uint32_t lo = be << (8 * s4), hi = s4 ? be >> (32 - 8 * s4) : 0u;
+        const int x0 = (int)q0 - (int)(4u * s);
+#pragma unroll
+        for (int k = 0; k < kQRows; ++k) {
+            const int x = x0 - 64 * k;
+            if (__builtin_amdgcn_ballot_w64(x >= -1 && x < 4) == 0)
+                continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                out[k][j] |= x == j ? lo : (x == j - 1 ? hi : 0u);
+        }
+    }
+    if (act) {
+        const uint32_t obase = o * dstride;
+#pragma unroll
+        for (int k = 0; k < kQRows; ++k) {
+            const uint32_t c = 16u * k + s;
+            if (16u * c < dstride)
+                __builtin_amdgcn_raw_buffer_store_b128(v4u{out[k][0], out[k][1], out[k][2], out[k][3]}, rout,
+                                                       obase + 16u * c, 0, kAuxST);
+        }
+        if (s == 0)
+            dlen[o] = (uint16_t)(valid ? n + 4u : 0u);
+    }
+}
+
+// Encode + SIM_FEC framing in one pass (rfec_wire_encode_fec): k_frame_fec_q
+// with its load stage replaced.  Datagram d = G n + l is line l of group G;
+// its payload windows are the XOR over the line's members (rows G k + first +
+// m stride of `shards`) of the windows k_frame_fec_q loads from a parity slot,
+// so no parity, meta, size or status array exists.  The field dwords: lanes
+// 0-5 the stamp, lanes 6-10 the XOR of one rfec_hdr dword over the members
+// (fec_meta, as meta_block_in of rfec_kernels.hip), lane 11 the maximum of
+// their sizes (fec_data_size); the status rule (fewer than 2 members, or a
+// size above the capacity) is taken in registers after the gather.
+//
+// The four quads of a wave have their own lines (4 / 4 / 2 members in a
+// 10 x 4 row plan, strided members on column lines): the plan's lines sit in
+// LDS behind the CRC tables, each quad reads its own, and the member loop
+// runs while any lane has a member left; a lane whose line is shorter loads
+// from past the descriptor (zeros, no memory access).  Windows whose payload
+// bytes start at or past 16 CD are not loaded (razor_fec.h, "Slot tails").
+// As in k_frame_fec_q the next quad's first member and stamp are issued at
+// the bottom of the loop, MF further members at a time at its top.
+//
+// Registers: the accumulator's 20 and 20 per member in flight, beside what
+// the framing needs.  Capped at 64 for 8 waves per SIMD (two blocks per CU)
+// with one member in flight it spills (8 VGPRs, 36 B of scratch per lane) and
+// is the slowest; at 4 waves (one block per CU, up to 128 registers) nothing
+// spills: 83 / 116 / 118 / 125 VGPRs for 1 / 2 / 3 / 4 members in flight.
+// Fused kernel, us (65,536 groups; c3, c3full at 1,216 / 1,280-byte slots, c5
+// at 256 / 320; the two calls of the same runs took 271-276 / 475-479 /
+// 248-255):
+//     waves, in flight     c3      c3full   c5
+//     8, 1 (spills)        224.9   417.6    221.0
+//     4, 1                 215.9   394.9    215.3
+//     4, 2                 213.4   390.8    220.8
+//     4, 3                 210.8   385.4    199.1   <- built
+//     4, 4                 212.2   391.1    221.2
+#ifndef RFEC_WEF_WAVES // (a measurement build may set both)
+#define RFEC_WEF_WAVES 4
+#define RFEC_WEF_IN_FLIGHT 3
+#endif
+constexpr int kWefWaves = RFEC_WEF_WAVES, kWefInFlight = RFEC_WEF_IN_FLIGHT;
+
+template <int WAVES, int MF>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES))) void k_encode_frame_fec_q(
+    const uint8_t* __restrict__ shards, const rfec_hdr* __restrict__ hdr, const rfec_fec_stamp* __restrict__ stamps,
+    const uint32_t* __restrict__ order, uint8_t* __restrict__ dgram, uint16_t* __restrict__ dlen, uint32_t groups,
+    uint32_t rows_out, uint32_t stride, uint32_t capacity, uint32_t dstride, uint32_t ndiv, rfec_kplan P)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t T[kQTabDwords + RFEC_MAX_LINES];
+    static_assert(sizeof(rfec_line) == 4, "a plan line is one dword: first | stride << 8 | count << 16");
+    uint32_t* PL = T + kQTabDwords;
+    const uint32_t lane = threadIdx.x & (kWave - 1), g = lane >> 4, s = lane & 15u;
+    const uint32_t n = P.n_lines, K = P.k, count = groups * n;
+    const uint32_t nquads = (count + 3u) / 4u;
+    const uint32_t nw = gridDim.x * kWavesPerBlock;
+    const uint32_t CD = (capacity + 15u) / 16u;
+    uint32_t q = wave_id();
+    const __amdgpu_buffer_rsrc_t rin = rsrc64(shards, (uint64_t)groups * K * stride);
+    const __amdgpu_buffer_rsrc_t rhd = rsrc64(hdr, (uint64_t)groups * K * sizeof(rfec_hdr));
+    const __amdgpu_buffer_rsrc_t rst = rsrc64(stamps, (uint64_t)count * sizeof(rfec_fec_stamp));
+    const __amdgpu_buffer_rsrc_t rout = rsrc64(dgram, (uint64_t)rows_out * dstride);
+    constexpr uint32_t kOut = 0xFFFFFFF0u;
+    // datagram d's line: its first member's row, the row step and the member count
+    // (ndiv = 2^32 / n + 1: exact for d n < 2^32, which the launch's bounds give)
+    auto line_of = [&](uint32_t d, bool act, uint32_t& row0, uint32_t& step, uint32_t& cnt) {
+        const uint32_t dd = act ? d : 0u;
+        const uint32_t G = n == 1 ? dd : __umulhi(dd, ndiv);
+        const uint32_t ln = PL[dd - G * n];
+        row0 = G * K + (ln & 0xffu);
+        step = (ln >> 8) & 0xffu;
+        cnt = act ? (ln >> 16) & 0xffu : 0u;
+    };
+    // one member's windows (chunk c >= 3: payload bytes from 16 (c - 3); chunk 2: from 0; chunks 0-1
+    // hold header bytes only) and its header dword for lanes 6-11 (lane 11: the size)
+    auto load_member = [&](uint32_t row, bool on, v4u (&X)[kQRows], uint32_t& hv) {
+        const uint32_t pbase = row * stride;
+#pragma unroll
+        for (int k = 0; k < kQRows; ++k) {
+            const uint32_t c = 16u * k + s, j = c >= 3 ? c - 3u : 0u;
+            X[k] = __builtin_bit_cast(
+                v4u, __builtin_amdgcn_raw_buffer_load_b128(rin, on && c >= 2 && j < CD ? pbase + 16u * j : kOut, 0,
+                                                           kAuxNT));
+        }
+        const uint32_t f = s - 6u;
+        const uint32_t v =
+            __builtin_amdgcn_raw_buffer_load_b32(rhd, on && f < 6u ? 20u * row + 4u * min(f, 4u) : kOut, 0, kAuxNT);
+        hv = s == 11 ? v >> 16 : v;
+    };
+    v4u W[kQRows];
+    uint32_t fv;
+    auto load_first = [&](uint32_t qq) {
+        const uint32_t dd = 4u * qq + g;
+        const bool a = dd < count;
+        uint32_t row0, step, cnt;
+        line_of(dd, a, row0, step, cnt);
+        load_member(row0, cnt > 0, W, fv);
+        fv |= __builtin_amdgcn_raw_buffer_load_b32(rst, a && s < 6 ? 24u * dd + 4u * s : kOut, 0, kAuxNT);
+    };
+    if (threadIdx.x < RFEC_MAX_LINES)
+        PL[threadIdx.x] = reinterpret_cast<const uint32_t*>(P.line)[threadIdx.x];
+    fill_tables(T);
+    __syncthreads();
+    if (q >= nquads)
+        return;
+    load_first(q);
+    for (;;) {
+        const uint32_t d = 4u * q + g;
+        const bool act = d < count;
+        uint32_t row0, step, cnt;
+        line_of(d, act, row0, step, cnt);
+        // members 1 .. cnt - 1, MF at a time (wave-uniform trip count: the longest line of the four)
+        for (uint32_t m = 1; __builtin_amdgcn_ballot_w64(m < cnt) != 0; m += MF) {
+            v4u X[MF][kQRows];
+            uint32_t hv[MF];
+#pragma unroll
+            for (int u = 0; u < MF; ++u)
+                load_member(row0 + (m + u) * step, m + u < cnt, X[u], hv[u]);
+#pragma unroll
+            for (int u = 0; u < MF; ++u) {
+#pragma unroll
+                for (int k = 0; k < kQRows; ++k)
+                    W[k] ^= X[u][k];
+                fv = s == 11 ? max(fv, hv[u]) : fv ^ hv[u];
+            }
+        }
+        const uint32_t o = order ? order[act ? d : 0u] : d;
+        uint32_t F[13];
+#pragma unroll
+        for (int i = 0; i < 13; ++i)
+            F[i] = bperm(fv, 16u * g + i);
+        const bool valid = cnt > 1 && F[11] <= capacity;
+        frame_fec_store_q(T, W, F, valid, act, o, s, rout, dlen, dstride);
+        q += nw;
+        if (q >= nquads)
+            break;
+        load_first(q);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Quarter-wave parse (slots of at most 1,280 bytes, or datagrams that fit
 // 1,280 bytes; payload slots of at most 1,280 bytes): the framing's layout
@@ -2010,6 +2233,28 @@ int rfec_launch_wire_frame_fec(uint32_t count, uint32_t stride, uint32_t capacit
     } else // slots above 1,280 bytes (or a batch past 32-bit buffer offsets): 32-byte lanes
         RFEC_LAUNCH(k_frame_fec<32>, dim3(grid_for<1>((const void*)k_frame_fec<32>, count)), dim3(kBlock), 0, sm,
                            parity, meta, fec_size, status, stamps, order, dgram, dlen, count, stride, capacity, dstride);
+    return (int)hipGetLastError();
+}
+
+// One launch of the fused encode + framing over `groups` groups (rfec_wire_fused.c splits a batch so that every
+// launch's inputs and output keep 32-bit buffer offsets: quarter_ok's bound, restated there); rows_out: the
+// datagram slots `dgram` holds (the launch's own, or with `order` the whole batch's).
+int rfec_launch_wire_encode_fec(const rfec_kplan* P, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                const uint8_t* shards, const rfec_hdr* hdr, const rfec_fec_stamp* stamps,
+                                const uint32_t* order, uint32_t dstride, uint8_t* dgram, uint16_t* dlen,
+                                uint32_t rows_out, void* stream)
+{
+    hipStream_t sm = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t n = P->n_lines, count = groups * n;
+    const uint64_t rows = (uint64_t)groups * P->k;
+    if (dstride > kQWindow || dstride % 16 || stride % 4 || (rows + 4) * stride + kQWindow >= 0xFFFFFFF0ull ||
+        rows * sizeof(rfec_hdr) >= 0xFFFFFFF0ull || (uint64_t)rows_out * dstride >= 0xFFFFFFF0ull || rows_out < count)
+        return (int)hipErrorInvalidValue;
+    const uint32_t ndiv = n > 1 ? (uint32_t)(0x100000000ull / n) + 1u : 0u;
+    const uint32_t quads = (count + 3u) / 4u;
+    RFEC_LAUNCH((k_encode_frame_fec_q<kWefWaves, kWefInFlight>),
+                dim3(grid_for<9>((const void*)k_encode_frame_fec_q<kWefWaves, kWefInFlight>, quads)), dim3(kBlock), 0,
+                sm, shards, hdr, stamps, order, dgram, dlen, groups, rows_out, stride, capacity, dstride, ndiv, *P);
     return (int)hipGetLastError();
 }
 

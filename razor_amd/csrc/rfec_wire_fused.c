@@ -1,0 +1,82 @@
+/*
+ * rfec_wire_fused.c -- rfec_wire_encode_fec (razor_fec.h, wire codec): a
+ * batch of groups straight into SIM_FEC datagrams, the encode and the framing
+ * in one kernel (k_encode_frame_fec_q, rfec_wire.hip): argument checks, then
+ * the launches through rfec_launch_wire_encode_fec, split over groups so that
+ * every launch keeps 32-bit buffer offsets.
+ *
+ * Not one of build.py's HOST_SRC: the CPU builds of the host layer link
+ * against a stub of the HIP runtime, which has no launch shims.
+ */
+#include <stdlib.h>
+
+#include "razor_fec.h"
+#include "rfec_internal.h"
+#include "rfec_host_internal.h"
+
+#define WEF_MAX_DSTRIDE 1280u        /* the quarter-wave window */
+#define WEF_OFFSETS 0xFFFFFFF0ull    /* buffer offsets stay below this */
+
+static int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+/* The most groups one launch takes: (groups k + 4) stride + 1280 (the bound the quarter-wave framing states for
+ * its input slots), the header records' groups k 20 bytes and, when the launch's output is its own slice of
+ * dgram (own_out), groups n dstride, all below WEF_OFFSETS.  At least 1: a group is at most 255 slots of 2 KiB. */
+static uint32_t groups_per_launch(const rfec_plan* p, uint32_t stride, uint32_t dstride, int own_out)
+{
+    const uint64_t k = p->k, n = p->n_lines;
+    uint64_t g = ((WEF_OFFSETS - 1 - WEF_MAX_DSTRIDE) / stride - 4) / k;
+    const uint64_t gh = (WEF_OFFSETS - 1) / (k * sizeof(rfec_hdr));
+    g = gh < g ? gh : g;
+    if (own_out) {
+        const uint64_t go = (WEF_OFFSETS - 1) / (n * dstride);
+        g = go < g ? go : g;
+    }
+    const char* v = getenv("RFEC_WIRE_ENCODE_CHUNK_GROUPS"); /* tests: a cap, to split a small batch */
+    if (v && atoi(v) > 0 && (uint64_t)atoi(v) < g)
+        g = (uint64_t)atoi(v);
+    return (uint32_t)(g < 1 ? 1 : g);
+}
+
+int rfec_wire_encode_fec(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                         const uint8_t* shards, const rfec_hdr* hdr, const rfec_fec_stamp* stamps,
+                         const uint32_t* order, uint32_t dstride, uint8_t* dgram, uint16_t* dlen, void* stream)
+{
+    int rc = check_plan(plan, RFEC_MAX_K_ENCODE);
+    if (rc)
+        return rc;
+    const uint32_t n = plan->n_lines;
+    if ((uint64_t)groups * n > 0xFFFFFFFFull)
+        return set_err(RFEC_EINVAL, "groups * n_lines overflows", 0);
+    if ((rc = check_wire(groups * n, stride, capacity, dstride, RFEC_WIRE_FEC_OVERHEAD)))
+        return rc;
+    if (dstride > WEF_MAX_DSTRIDE)
+        return set_err(RFEC_EINVAL,
+                       "rfec_wire_encode_fec takes dstride <= 1280: use rfec_encode_batch + rfec_wire_frame_fec", 0);
+    if (groups == 0 || n == 0)
+        return RFEC_OK;
+    if (!shards || !hdr || !stamps || !dgram || !dlen)
+        return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if (misaligned(shards, 16) || misaligned(dgram, 16))
+        return set_err(RFEC_EINVAL, "shards and dgram must be 16-byte aligned", 0);
+    if (misaligned(hdr, 4) || misaligned(stamps, 4) || misaligned(order, 4))
+        return set_err(RFEC_EINVAL, "hdr, stamps and order must be 4-byte aligned", 0);
+    if (misaligned(dlen, 2))
+        return set_err(RFEC_EINVAL, "dlen must be 2-byte aligned", 0);
+    const uint32_t count = groups * n;
+    if (order && (uint64_t)count * dstride >= WEF_OFFSETS)
+        return set_err(RFEC_EINVAL, "with order, the datagram slots must stay below 4 GiB", 0);
+    const uint32_t per = groups_per_launch(plan, stride, dstride, order == NULL);
+    for (uint32_t g0 = 0; g0 < groups; g0 += per) {
+        const uint32_t ng = groups - g0 < per ? groups - g0 : per;
+        const size_t r0 = (size_t)g0 * plan->k, d0 = (size_t)g0 * n;
+        /* without order a launch writes its own slots; with it, anywhere in the batch's */
+        const int e = rfec_launch_wire_encode_fec(plan, ng, stride, capacity, shards + r0 * stride, hdr + r0,
+                                                  stamps + d0, order ? order + d0 : NULL, dstride,
+                                                  order ? dgram : dgram + d0 * dstride, order ? dlen : dlen + d0,
+                                                  order ? count : ng * n, stream);
+        if (e)
+            return set_err(RFEC_EDEVICE, "wire_encode_fec launch", e);
+    }
+    return RFEC_OK;
+}

@@ -231,6 +231,8 @@ _SIGS = {
     "rfec_wire_frame_fec": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint32, _P,
                                       _P, _P]),
     "rfec_wire_frame_seg": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    "rfec_wire_encode_fec": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P,
+                                       C.c_uint32, _P, _P, _P]),
     "rfec_wire_parse": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
@@ -459,6 +461,14 @@ class Native:
                        order=None):
         self._check(self.lib.rfec_wire_frame_seg(count, stride, capacity, shards, hdr, stamps, order, dstride, dgram,
                                                  dlen, stream), "rfec_wire_frame_seg")
+
+    def wire_encode_fec(self, plan, groups, stride, capacity, shards, hdr, stamps, dstride, dgram, dlen, stream=None,
+                        order=None):
+        """rfec_wire_encode_fec: `groups` groups straight into their SIM_FEC datagrams, one kernel for
+        rfec_encode_batch + rfec_wire_frame_fec (slots up to 1,280 bytes)."""
+        self._check(self.lib.rfec_wire_encode_fec(C.byref(as_plan(plan)), groups, stride, capacity, shards, hdr,
+                                                  stamps, order, dstride, dgram, dlen, stream),
+                    "rfec_wire_encode_fec")
 
     def wire_parse(self, n, dstride, dgram, dlen, stride, capacity, recs, payload, stream=None):
         self._check(self.lib.rfec_wire_parse(n, dstride, dgram, dlen, stride, capacity, recs, payload, stream),
