@@ -185,8 +185,9 @@ int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec
  *             aligned one with 32-bit loads, same result)
  *    2 bytes  fec_size
  *    1 byte   status, out_index
- * (rfec_wire_encode_fec, the one wire-codec call that checks alignment: 16
- * bytes shards and dgram, 4 bytes hdr, stamps and order, 2 bytes dlen)
+ * (rfec_wire_encode_fec and rfec_wire_encode_send, the wire-codec calls that
+ * check alignment: 16 bytes shards and the datagram slots, 4 bytes hdr, stamps
+ * and orders, 2 bytes the lengths)
  *
  * Slot tails.  Every call works on the CD = ceil(capacity / 16) leading
  * 16-byte chunks of a slot (CD = 1 for capacity 0) and touches no byte of any
@@ -396,7 +397,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_parse) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_parse) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -504,6 +505,42 @@ int rfec_wire_frame_seg(uint32_t count, uint32_t stride, uint32_t capacity, cons
 int rfec_wire_encode_fec(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
                          const uint8_t* shards, const rfec_hdr* hdr, const rfec_fec_stamp* stamps,
                          const uint32_t* order, uint32_t dstride, uint8_t* dgram, uint16_t* dlen, void* stream);
+
+/* Every datagram of a batch of groups in one kernel: the k SIM_SEG datagrams
+ * of each group and its n_lines SIM_FEC datagrams.  With ns = groups * plan->k
+ * and nf = groups * plan->n_lines, seg_dgram [ns][dstride] / seg_dlen [ns] are
+ * byte for byte what
+ *   rfec_wire_frame_seg(ns, stride, capacity, shards, hdr, seg_stamps,
+ *                       seg_order, dstride, seg_dgram, seg_dlen, ...)
+ * writes and fec_dgram [nf][dstride] / fec_dlen [nf] what
+ *   rfec_wire_encode_fec(plan, groups, stride, capacity, shards, hdr,
+ *                        fec_stamps, fec_order, dstride, fec_dgram, fec_dlen, ...)
+ * writes on the same inputs, whole slots (a segment whose data_size exceeds
+ * capacity gets length 0 and a zero slot; a line is refused as there).  Every
+ * member is read once per line it sits on -- on a rows-only plan once, for its
+ * SIM_SEG and its row's parity together -- and a member that sits on no line
+ * once, for its SIM_SEG ("Slot tails": the shards' bytes from 16 * CD to the
+ * stride are not read).  Any plan with k <= RFEC_MAX_K_ENCODE; with
+ * n_lines == 0 only the segments are framed and the four SIM_FEC pointers are
+ * not touched (they may be NULL).  groups == 0 touches nothing: every pointer
+ * may be NULL.  Each order may be NULL, as for rfec_wire_frame_fec.
+ * The four outputs must not overlap each other or any input (not checked).
+ * Alignment (RFEC_EINVAL for less): 16 bytes shards, seg_dgram and fec_dgram,
+ * 4 bytes hdr, both stamp arrays and both orders, 2 bytes seg_dlen and
+ * fec_dlen.  dstride >= capacity + 49 (the SIM_FEC overhead, which covers the
+ * SIM_SEG's 36) and dstride <= 1280: above that RFEC_EINVAL -- use
+ * rfec_wire_frame_seg + rfec_wire_encode_fec.  A batch of any size is taken
+ * (split over several launches so that every launch keeps 32-bit buffer
+ * offsets); with seg_order, ns * dstride must stay below 4 GiB, with
+ * fec_order nf * dstride (RFEC_EINVAL).  RFEC_WIRE_ENCODE_CHUNK_GROUPS caps
+ * the groups per launch as for rfec_wire_encode_fec. */
+int rfec_wire_encode_send(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                          const uint8_t* shards, const rfec_hdr* hdr,
+                          const rfec_seg_stamp* seg_stamps, const uint32_t* seg_order,
+                          uint8_t* seg_dgram, uint16_t* seg_dlen,
+                          const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
+                          uint8_t* fec_dgram, uint16_t* fec_dlen,
+                          uint32_t dstride, void* stream);
 
 /* Parse status (rfec_wire_rec.status). */
 #define RFEC_WIRE_OK 0         /* SIM_SEG / SIM_FEC decoded (a SEG with a bad data length decodes

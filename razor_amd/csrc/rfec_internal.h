@@ -131,6 +131,18 @@ int rfec_launch_wire_encode_fec(const rfec_kplan* P, uint32_t groups, uint32_t s
                                 const uint8_t* shards, const rfec_hdr* hdr, const rfec_fec_stamp* stamps,
                                 const uint32_t* order, uint32_t dstride, uint8_t* dgram, uint16_t* dlen,
                                 uint32_t rows_out, void* stream);
+/* rfec_wire_encode_send (rfec_wire_fused.c): one launch of the fused SIM_SEG framing + encode + SIM_FEC framing
+ * over `groups` groups; segment g * k + i -> slot seg_order[...] (or its own index) of seg_dgram, which holds
+ * seg_rows_out slots, datagram g * n_lines + l likewise into fec_dgram's fec_rows_out slots.  The caller keeps
+ * (groups * k + 4) * stride + 1280, groups * k * 20 and both rows_out * dstride below 0xFFFFFFF0 and
+ * dstride <= 1280, stride a multiple of 16; hipErrorInvalidValue otherwise.  With n_lines == 0 the FEC pointers
+ * are not touched. */
+int rfec_launch_wire_encode_send(const rfec_kplan* P, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                 const uint8_t* shards, const rfec_hdr* hdr, const rfec_seg_stamp* seg_stamps,
+                                 const uint32_t* seg_order, uint8_t* seg_dgram, uint16_t* seg_dlen,
+                                 uint32_t seg_rows_out, const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
+                                 uint8_t* fec_dgram, uint16_t* fec_dlen, uint32_t fec_rows_out, uint32_t dstride,
+                                 void* stream);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */
 int rfec_launch_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const uint16_t* dlen,

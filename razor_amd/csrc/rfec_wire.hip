@@ -1419,10 +1419,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc64(const void* p, uint64_t
 }
 
 // bytes >= m of a quarter-wave's chunks to zero (rows that some lane's range ends in or before)
-__device__ __forceinline__ void mask_q(uint32_t (&x)[kQRows][4], uint32_t m, uint32_t s)
+template <int NR>
+__device__ __forceinline__ void mask_q(uint32_t (&x)[NR][4], uint32_t m, uint32_t s)
 {
 #pragma unroll
-    for (int k = 0; k < kQRows; ++k) {
+    for (int k = 0; k < NR; ++k) {
         const int e = (int)m - (int)(16u * (16u * k + s));
         if (__builtin_amdgcn_ballot_w64(e < 16) != 0) {
 #pragma unroll
@@ -1745,7 +1746,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) voi
 // out 4 instructions longer with other registers (101.1 / 101.8 us against 102.1 / 102.9 in bench.py --full
 // of the parent and of the tree alternating, inside the +-1 us that identical code shows between runs), so
 // its body stays as it was and compiles to the same instructions as before.
-__device__ __forceinline__ void frame_fec_store_q(const uint32_t* T, const v4u (&W)[kQRows], const uint32_t (&F)[13],
+template <int NR>
+__device__ __forceinline__ void frame_fec_store_q(const uint32_t* T, const v4u (&W)[NR], const uint32_t (&F)[13],
                                                   bool valid, bool act, uint32_t o, uint32_t s,
                                                   __amdgpu_buffer_rsrc_t rout, uint16_t* __restrict__ dlen,
                                                   uint32_t dstride)
@@ -1759,16 +1761,16 @@ __device__ __forceinline__ void frame_fec_store_q(const uint32_t* T, const v4u (
         const uint32_t h0 = fec_hdr_dword(F, j), h1 = fec_hdr_dword(F, 4 + j), h2 = fec_hdr_dword(F, 8 + j);
         Hd[j] = s == 0 ? h0 : (s == 1 ? h1 : (s == 2 ? h2 : 0u));
     }
-    uint32_t out[kQRows][4];
+    uint32_t out[NR][4];
     {
-        uint32_t nx[kQRows];
+        uint32_t nx[NR];
 #pragma unroll
-        for (int k = 0; k < kQRows; ++k)
+        for (int k = 0; k < NR; ++k)
             nx[k] = dpp(W[k][0], kDppRowRor15);
 #pragma unroll
-        for (int k = 0; k < kQRows; ++k) {
+        for (int k = 0; k < NR; ++k) {
             uint32_t w[5] = {W[k][0], W[k][1], W[k][2], W[k][3],
-                             s == 15 ? (k + 1 < kQRows ? nx[k + 1 < kQRows ? k + 1 : k] : 0u) : nx[k]};
+                             s == 15 ? (k + 1 < NR ? nx[k + 1 < NR ? k + 1 : k] : 0u) : nx[k]};
             if (k == 0) { // lanes 0-1: header only; lane 2: payload bytes 0-2 at its end
                 const uint32_t p0 = w[0];
 #pragma unroll
@@ -1788,11 +1790,11 @@ __device__ __forceinline__ void frame_fec_store_q(const uint32_t* T, const v4u (
     // CRC32 (Horner over the rows, seed folded into the first dword)
     uint32_t acc = 0;
 #pragma unroll
-    for (int k = 0; k < kQRows; ++k) {
+    for (int k = 0; k < NR; ++k) {
         const uint32_t x0 = out[k][0] ^ (k == 0 && s == 0 ? ~RFEC_WIRE_CRC_SEED : 0u);
         acc = (k ? mul_row(T, acc) : 0u) ^ slice16(T, x0, out[k][1], out[k][2], out[k][3]);
     }
-    const uint32_t D = kQWindow - n, Dq = D >> 4, Dr = D & 15u;
+    const uint32_t D = 256u * NR - n, Dq = D >> 4, Dr = D & 15u;
     const uint32_t R = row_xor(carry_q(T, acc, s + Dq));
     const uint32_t* iv = T + kQInv + Dr * 32u;
     const uint32_t b = (((R >> s) & 1u) ? iv[s] : 0u) ^ (((R >> (s + 16u)) & 1u) ? iv[s + 16u] : 0u);
@@ -1802,7 +1804,7 @@ __device__ __forceinline__ void frame_fec_store_q(const uint32_t* T, const v4u (
         const uint32_t lo = be << (8 * s4), hi = s4 ? be >> (32 - 8 * s4) : 0u;
         const int x0 = (int)q0 - (int)(4u * s);
 #pragma unroll
-        for (int k = 0; k < kQRows; ++k) {
+        for (int k = 0; k < NR; ++k) {
             const int x = x0 - 64 * k;
             if (__builtin_amdgcn_ballot_w64(x >= -1 && x < 4) == 0)
                 continue;
@@ -1814,7 +1816,7 @@ __device__ __forceinline__ void frame_fec_store_q(const uint32_t* T, const v4u (
     if (act) {
         const uint32_t obase = o * dstride;
 #pragma unroll
-        for (int k = 0; k < kQRows; ++k) {
+        for (int k = 0; k < NR; ++k) {
             const uint32_t c = 16u * k + s;
             if (16u * c < dstride)
                 __builtin_amdgcn_raw_buffer_store_b128(v4u{out[k][0], out[k][1], out[k][2], out[k][3]}, rout,
@@ -1958,6 +1960,273 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
         if (q >= nquads)
             break;
         load_first(q);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// A batch's SIM_SEG and SIM_FEC datagrams in one pass (rfec_wire_encode_send):
+// every member's payload is loaded once per line it sits on, framed as its
+// SIM_SEG from those registers and XORed into its line's parity, which is
+// framed as the line's SIM_FEC when the line ends.
+//
+// Unit of work: four consecutive groups per wave, one group per quad of 16
+// lanes.  The four quads walk the same plan, so the walk over lines and
+// members is wave-uniform (scalar branches); a quad past the batch's end runs
+// with its loads and stores off.  A member's SIM_SEG is framed on the first
+// line that holds it (own[], from the launch shim); members that no line
+// holds are framed after the lines.  On a matrix plan the column lines load
+// their members a second time, as k_encode_frame_fec_q does.
+//
+// Alignment.  The XOR needs every member at the same alignment, the SIM_SEG
+// header is 26-32 bytes by the member's field widths.  Lane c = 16 k + s of a
+// quad loads payload bytes [16 (c - 2), 16 (c - 1)) of every member, aligned
+// 16-byte loads (k_frame_seg_q's start at dword 4 c - hs / 4): the accumulator
+// takes them as they are, and the member's SIM_SEG chunk c -- payload bytes
+// from 16 c - hs = 16 (c - 2) + t, t = 32 - hs in {0, 2, 4, 6} -- is the
+// window with the next lane's first two dwords behind it, moved down by t / 4
+// dwords (a per-lane select) and t % 4 bytes (v_alignbyte).  Lanes 0-1 load
+// nothing: chunk 1 then comes out as 16 - t zero bytes, where the header's end
+// goes, and the payload's first t.  SIM_FEC chunk c holds payload bytes from
+// 16 c - 45 = 16 (c - 3) + 3: the accumulator one lane up (row_ror:1; lane 0
+// takes lane 15's of the row before) is what k_frame_fec_q loads, and
+// frame_fec_store_q takes it from there.
+// ---------------------------------------------------------------------------
+struct SendOwn {
+    uint32_t w[64]; // byte i: the line that frames member i's SIM_SEG, 0xFF: none holds it
+};
+
+__device__ __forceinline__ uint32_t row_ror1(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x121, 0xF, 0xF, false); // lane i reads lane (i - 1) mod 16
+}
+
+// k_frame_seg_q's stage after its loads, from the aligned windows W (lane c: payload bytes from 16 (c - 2),
+// zero for c < 2): the funnel by 32 - hs bytes, the header over chunks 0-1, the mask at the length, the CRC32 and
+// its trailer, the stores.  HB: the wave's header batch in LDS (dword f of lane i's header at f * 64 + i, the
+// packed facts m at f = 8), src: the lane that computed this datagram's.
+template <int NR>
+__device__ __forceinline__ void frame_seg_store_a(const uint32_t* T, const v4u (&W)[NR], const uint32_t* HB,
+                                                  uint32_t src, bool act, uint32_t o, uint32_t s,
+                                                  __amdgpu_buffer_rsrc_t rout, uint16_t* __restrict__ dlen,
+                                                  uint32_t dstride, uint32_t rows_out)
+{
+    const uint32_t mc = HB[8 * kWave + src];
+    const uint32_t hs = (mc >> 16) & 63u, L = mc & 0xffffu;
+    const bool valid = (mc >> 31) != 0;
+    const uint32_t n = valid ? hs + L : 0u; // invalid: every byte masked, length 0
+    const uint32_t sh = hs & 2u;            // (32 - hs) mod 4 for an even hs
+    const bool dw = hs < 30u;               // 32 - hs >= 4: one dword down first
+    uint32_t out[NR][4];
+    {
+        uint32_t n0[NR], n1[NR];
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            n0[k] = dpp(W[k][0], kDppRowRor15);
+            n1[k] = dpp(W[k][1], kDppRowRor15);
+        }
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            // the next chunk's first two dwords: lane s + 1's, for s = 15 lane 0's in the next row
+            const uint32_t a4 = s == 15 ? (k + 1 < NR ? n0[k + 1 < NR ? k + 1 : k] : 0u) : n0[k];
+            const uint32_t a5 = s == 15 ? (k + 1 < NR ? n1[k + 1 < NR ? k + 1 : k] : 0u) : n1[k];
+            const uint32_t w[6] = {W[k][0], W[k][1], W[k][2], W[k][3], a4, a5};
+            uint32_t x[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j)
+                x[j] = dw ? w[j + 1] : w[j];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                out[k][j] = __builtin_amdgcn_alignbyte(x[j + 1], x[j], sh);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    { // the header's dwords j and 4 + j, taken by lanes 0 and 1
+        const uint32_t h0 = HB[j * kWave + src], h1 = HB[(4 + j) * kWave + src];
+        out[0][j] |= s == 0 ? h0 : (s == 1 ? h1 : 0u);
+    }
+    mask_q(out, n, s);
+    // CRC32 (Horner over the rows, seed folded into the first dword)
+    uint32_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        const uint32_t x0 = out[k][0] ^ (k == 0 && s == 0 ? ~RFEC_WIRE_CRC_SEED : 0u);
+        acc = (k ? mul_row(T, acc) : 0u) ^ slice16(T, x0, out[k][1], out[k][2], out[k][3]);
+    }
+    const uint32_t D = 256u * NR - n, Dq = D >> 4, Dr = D & 15u;
+    const uint32_t R = row_xor(carry_q(T, acc, s + Dq));
+    const uint32_t* iv = T + kQInv + Dr * 32u;
+    const uint32_t b = (((R >> s) & 1u) ? iv[s] : 0u) ^ (((R >> (s + 16u)) & 1u) ? iv[s + 16u] : 0u);
+    const uint32_t crc = ~row_xor(b);
+    if (valid) { // big-endian trailer at byte n
+        const uint32_t be = bswap(crc), s4 = n & 3u, q0 = n >> 2;
+        const uint32_t lo = be << (8 * s4), hi = s4 ? be >> (32 - 8 * s4) : 0u;
+        const int x0 = (int)q0 - (int)(4u * s);
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const int x = x0 - 64 * k;
+            if (__builtin_amdgcn_ballot_w64(x >= -1 && x < 4) == 0)
+                continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                out[k][j] |= x == j ? lo : (x == j - 1 ? hi : 0u);
+        }
+    }
+    if (act) {
+        const uint32_t obase = o * dstride;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const uint32_t c = 16u * k + s;
+            if (16u * c < dstride)
+                __builtin_amdgcn_raw_buffer_store_b128(v4u{out[k][0], out[k][1], out[k][2], out[k][3]}, rout,
+                                                       obase + 16u * c, 0, kAuxST);
+        }
+        if (s == 0 && o < rows_out)
+            dlen[o] = (uint16_t)(valid ? n + 4u : 0u);
+    }
+}
+
+// Registers: the accumulator's 20, a member's 20 and the SIM_SEG chunks' 20 beside the CRC's: 4 waves per SIMD
+// (one block per CU), as k_encode_frame_fec_q; 8 waves (64 VGPRs) cannot hold the three.  127 VGPRs, no scratch,
+// 51 SGPRs spilled to VGPR lanes (five descriptors and the plan walk's scalars); with the header batch in
+// registers (9 VGPRs, ds_bpermute): 128 VGPRs and 2 spilled.  No member is prefetched.
+// NR: the rows of 16 chunks a slot takes -- 2 for slots up to 512 bytes, else 5.  With five rows for every slot,
+// c5 (320-byte slots: 20 of a quad's 80 chunks) ran every stage over three empty rows, twice: 727 us against the
+// two calls' 660; with two rows (90 VGPRs) 465 against 657.  65,536 groups, us, against k_frame_seg_q +
+// k_encode_frame_fec_q in the same runs: c3 402 / 492, c3full 563 / 713.
+constexpr int kSendWaves = 4;
+
+template <int WAVES, int NR>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES))) void k_encode_send_q(
+    const uint8_t* __restrict__ shards, const rfec_hdr* __restrict__ hdr, const rfec_seg_stamp* __restrict__ sstamps,
+    const uint32_t* __restrict__ sorder, uint8_t* __restrict__ sdgram, uint16_t* __restrict__ sdlen,
+    uint32_t srows_out, const rfec_fec_stamp* __restrict__ fstamps, const uint32_t* __restrict__ forder,
+    uint8_t* __restrict__ fdgram, uint16_t* __restrict__ fdlen, uint32_t frows_out, uint32_t groups, uint32_t stride,
+    uint32_t capacity, uint32_t dstride, rfec_kplan P, SendOwn O)
+{
+    // behind the CRC tables: the plan's lines, own[] and, per wave, a batch of 64 SIM_SEG headers (9 dwords each:
+    // in registers and taken by ds_bpermute, as in k_frame_seg_q, they cost the 9 VGPRs this kernel lacks)
+    __shared__ __attribute__((aligned(16))) uint32_t T[kQTabDwords + RFEC_MAX_LINES + 64 + kWavesPerBlock * 9 * kWave];
+    static_assert(sizeof(rfec_line) == 4, "a plan line is one dword: first | stride << 8 | count << 16");
+    static_assert(RFEC_MAX_K_ENCODE <= 256 && RFEC_MAX_LINES < 0xFF, "own[] is a byte per member, 0xFF: no line");
+    uint32_t* PL = T + kQTabDwords;
+    uint32_t* OW = PL + RFEC_MAX_LINES;
+    uint32_t* HB = OW + 64 + (threadIdx.x >> 6) * (9 * kWave);
+    const uint32_t lane = threadIdx.x & (kWave - 1), g = lane >> 4, s = lane & 15u;
+    const uint32_t n = P.n_lines, K = P.k;
+    const uint32_t nunits = (groups + 3u) / 4u;
+    const uint32_t nw = gridDim.x * kWavesPerBlock;
+    const uint32_t CD = (capacity + 15u) / 16u;
+    const __amdgpu_buffer_rsrc_t rin = rsrc64(shards, (uint64_t)groups * K * stride);
+    const __amdgpu_buffer_rsrc_t rhd = rsrc64(hdr, (uint64_t)groups * K * sizeof(rfec_hdr));
+    const __amdgpu_buffer_rsrc_t rst = rsrc64(fstamps, (uint64_t)groups * n * sizeof(rfec_fec_stamp));
+    const __amdgpu_buffer_rsrc_t rso = rsrc64(sdgram, (uint64_t)srows_out * dstride);
+    const __amdgpu_buffer_rsrc_t rfo = rsrc64(fdgram, (uint64_t)frows_out * dstride);
+    constexpr uint32_t kOut = 0xFFFFFFF0u;
+    if (threadIdx.x < RFEC_MAX_LINES)
+        PL[threadIdx.x] = reinterpret_cast<const uint32_t*>(P.line)[threadIdx.x];
+    else if (threadIdx.x < RFEC_MAX_LINES + 64)
+        OW[threadIdx.x - RFEC_MAX_LINES] = O.w[threadIdx.x - RFEC_MAX_LINES];
+    fill_tables(T);
+    __syncthreads();
+    // one member's windows and, for lanes 6-11, its header dword (lane 11: the size), as k_encode_frame_fec_q's
+    auto load_member = [&](uint32_t row, bool on, v4u (&X)[NR], uint32_t& hv) {
+        const uint32_t pbase = row * stride;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const uint32_t c = 16u * k + s;
+            X[k] = __builtin_bit_cast(
+                v4u, __builtin_amdgcn_raw_buffer_load_b128(rin, on && c >= 2 && c - 2u < CD ? pbase + 16u * (c - 2u) : kOut,
+                                                           0, kAuxNT));
+        }
+        const uint32_t f = s - 6u;
+        const uint32_t v =
+            __builtin_amdgcn_raw_buffer_load_b32(rhd, on && f < 6u ? 20u * row + 4u * min(f, 4u) : kOut, 0, kAuxNT);
+        hv = s == 11 ? v >> 16 : v;
+    };
+    for (uint32_t u = wave_id(); u < nunits; u += nw) {
+        const uint32_t G = 4u * u + g;
+        const bool act = G < groups;
+        const uint32_t row_g = (act ? G : 0u) * K;
+        // SIM_SEG headers, 16 members of a line (or one orphan) at a time: lane 4 t + gg holds the header of
+        // group 4 u + gg's member first + (j0 + t) step
+        auto pass = [&](uint32_t first, uint32_t step, uint32_t j0, uint32_t cnt) {
+            const uint32_t Gp = 4u * u + (lane & 3u), jj = j0 + (lane >> 2);
+            const bool a = Gp < groups && jj < cnt;
+            const SegHdrQ B = seg_header_q(hdr, sstamps, a ? Gp * K + first + jj * step : 0u, a, capacity);
+            wave_lds_sync(); // the batch before this one has been read
+#pragma unroll
+            for (int f = 0; f < 8; ++f)
+                HB[f * kWave + lane] = B.h[f];
+            HB[8 * kWave + lane] = B.m;
+            wave_lds_sync();
+        };
+        auto frame_seg = [&](const v4u (&W)[NR], uint32_t bt, uint32_t i) {
+            const uint32_t src = 4u * bt + g, d = row_g + i;
+            const uint32_t o = sorder ? sorder[d] : d;
+            frame_seg_store_a(T, W, HB, src, act, o, s, rso, sdlen, dstride, srows_out);
+        };
+        auto owner = [&](uint32_t i) {
+            return (uint32_t)__builtin_amdgcn_readfirstlane((int)OW[i >> 2]) >> (8u * (i & 3u)) & 0xffu;
+        };
+        for (uint32_t l = 0; l < n; ++l) {
+            const uint32_t ln = (uint32_t)__builtin_amdgcn_readfirstlane((int)PL[l]);
+            const uint32_t first = ln & 0xffu, step = (ln >> 8) & 0xffu, cnt = (ln >> 16) & 0xffu;
+            const uint32_t fd = (act ? G : 0u) * n + l;
+            uint32_t fv = __builtin_amdgcn_raw_buffer_load_b32(rst, act && s < 6 ? 24u * fd + 4u * s : kOut, 0, kAuxNT);
+            v4u A[NR];
+#pragma unroll
+            for (int k = 0; k < NR; ++k)
+                A[k] = v4u{0u, 0u, 0u, 0u};
+            uint32_t j0 = 0xFFFFFFFFu; // the header batch holds members j0 .. j0 + 15 of this line
+            for (uint32_t j = 0; j < cnt; ++j) {
+                const uint32_t i = first + j * step;
+                v4u W[NR];
+                uint32_t hv;
+                load_member(row_g + i, act, W, hv);
+                const bool own = owner(i) == l;
+                if (own && (j & ~15u) != j0) {
+                    j0 = j & ~15u;
+                    pass(first, step, j0, cnt);
+                }
+#pragma unroll
+                for (int k = 0; k < NR; ++k)
+                    A[k] ^= W[k];
+                fv = s == 11 ? max(fv, hv) : fv ^ hv;
+                if (own)
+                    frame_seg(W, j & 15u, i);
+            }
+            // the line's SIM_FEC: the accumulator one lane up; lane 2 keeps payload dword 0 for chunk 2's end
+            v4u R[NR];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t r[NR];
+#pragma unroll
+                for (int k = 0; k < NR; ++k)
+                    r[k] = row_ror1(A[k][j]);
+#pragma unroll
+                for (int k = 0; k < NR; ++k)
+                    R[k][j] = s == 0 ? (k ? r[k ? k - 1 : 0] : 0u) : r[k];
+            }
+            R[0][0] = s == 2 ? A[0][0] : R[0][0];
+            const uint32_t o = forder ? forder[fd] : fd;
+            uint32_t F[13];
+#pragma unroll
+            for (int i = 0; i < 13; ++i)
+                F[i] = bperm(fv, 16u * g + i);
+            const bool valid = cnt > 1 && F[11] <= capacity;
+            frame_fec_store_q(T, R, F, valid, act, o, s, rfo, fdlen, dstride);
+        }
+        // members that no line holds
+        for (uint32_t i = 0; i < K; ++i) {
+            if (owner(i) != 0xFFu)
+                continue;
+            v4u W[NR];
+            uint32_t hv;
+            load_member(row_g + i, act, W, hv);
+            pass(i, 0u, 0u, 1u);
+            frame_seg(W, 0u, i);
+        }
     }
 }
 
@@ -2255,6 +2524,49 @@ int rfec_launch_wire_encode_fec(const rfec_kplan* P, uint32_t groups, uint32_t s
     RFEC_LAUNCH((k_encode_frame_fec_q<kWefWaves, kWefInFlight>),
                 dim3(grid_for<9>((const void*)k_encode_frame_fec_q<kWefWaves, kWefInFlight>, quads)), dim3(kBlock), 0,
                 sm, shards, hdr, stamps, order, dgram, dlen, groups, rows_out, stride, capacity, dstride, ndiv, *P);
+    return (int)hipGetLastError();
+}
+
+// One launch of rfec_wire_encode_send over `groups` groups (rfec_wire_fused.c splits a batch as for
+// rfec_launch_wire_encode_fec); seg_rows_out / fec_rows_out: the slots seg_dgram / fec_dgram hold.
+int rfec_launch_wire_encode_send(const rfec_kplan* P, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                 const uint8_t* shards, const rfec_hdr* hdr, const rfec_seg_stamp* seg_stamps,
+                                 const uint32_t* seg_order, uint8_t* seg_dgram, uint16_t* seg_dlen,
+                                 uint32_t seg_rows_out, const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
+                                 uint8_t* fec_dgram, uint16_t* fec_dlen, uint32_t fec_rows_out, uint32_t dstride,
+                                 void* stream)
+{
+    hipStream_t sm = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t n = P->n_lines, K = P->k;
+    const uint64_t rows = (uint64_t)groups * K, count = (uint64_t)groups * n;
+    if (K < 1 || K > RFEC_MAX_K_ENCODE || n > RFEC_MAX_LINES || dstride > kQWindow || dstride % 16 || stride % 16 ||
+        (rows + 4) * stride + kQWindow >= 0xFFFFFFF0ull || rows * sizeof(rfec_hdr) >= 0xFFFFFFF0ull ||
+        (uint64_t)seg_rows_out * dstride >= 0xFFFFFFF0ull || (uint64_t)fec_rows_out * dstride >= 0xFFFFFFF0ull ||
+        seg_rows_out < rows || fec_rows_out < count)
+        return (int)hipErrorInvalidValue;
+    // member i's SIM_SEG is framed on the first line that holds it
+    SendOwn O;
+    uint8_t* own = reinterpret_cast<uint8_t*>(O.w);
+    for (uint32_t i = 0; i < sizeof(O.w); ++i)
+        own[i] = 0xFF;
+    for (uint32_t l = n; l-- > 0;)
+        for (uint32_t j = 0; j < P->line[l].count; ++j) {
+            const uint32_t i = P->line[l].first + j * P->line[l].stride;
+            if (i >= K)
+                return (int)hipErrorInvalidValue;
+            own[i] = (uint8_t)l;
+        }
+    const uint32_t units = (groups + 3u) / 4u;
+    if (dstride <= 512u) // two rows of 16 chunks hold the slot
+        RFEC_LAUNCH((k_encode_send_q<kSendWaves, 2>),
+                    dim3(grid_for<11>((const void*)k_encode_send_q<kSendWaves, 2>, units)), dim3(kBlock), 0, sm, shards,
+                    hdr, seg_stamps, seg_order, seg_dgram, seg_dlen, seg_rows_out, fec_stamps, fec_order, fec_dgram,
+                    fec_dlen, fec_rows_out, groups, stride, capacity, dstride, *P, O);
+    else
+        RFEC_LAUNCH((k_encode_send_q<kSendWaves, kQRows>),
+                    dim3(grid_for<10>((const void*)k_encode_send_q<kSendWaves, kQRows>, units)), dim3(kBlock), 0, sm,
+                    shards, hdr, seg_stamps, seg_order, seg_dgram, seg_dlen, seg_rows_out, fec_stamps, fec_order,
+                    fec_dgram, fec_dlen, fec_rows_out, groups, stride, capacity, dstride, *P, O);
     return (int)hipGetLastError();
 }
 

@@ -3,7 +3,9 @@
  * batch of groups straight into SIM_FEC datagrams, the encode and the framing
  * in one kernel (k_encode_frame_fec_q, rfec_wire.hip): argument checks, then
  * the launches through rfec_launch_wire_encode_fec, split over groups so that
- * every launch keeps 32-bit buffer offsets.
+ * every launch keeps 32-bit buffer offsets.  rfec_wire_encode_send: the same
+ * for the batch's SIM_SEG and SIM_FEC datagrams in one kernel
+ * (k_encode_send_q).
  *
  * Not one of build.py's HOST_SRC: the CPU builds of the host layer link
  * against a stub of the HIP runtime, which has no launch shims.
@@ -77,6 +79,75 @@ int rfec_wire_encode_fec(const rfec_plan* plan, uint32_t groups, uint32_t stride
                                                   order ? count : ng * n, stream);
         if (e)
             return set_err(RFEC_EDEVICE, "wire_encode_fec launch", e);
+    }
+    return RFEC_OK;
+}
+
+/* groups_per_launch for rfec_wire_encode_send: the SIM_FEC output as there (own_fec), and groups k dstride of
+ * the SIM_SEG output below WEF_OFFSETS when the launch's slots are its own slice of seg_dgram (own_seg). */
+static uint32_t send_groups_per_launch(const rfec_plan* p, uint32_t stride, uint32_t dstride, int own_seg,
+                                       int own_fec)
+{
+    uint64_t g = groups_per_launch(p, stride, dstride, own_fec && p->n_lines > 0);
+    if (own_seg) {
+        const uint64_t gs = (WEF_OFFSETS - 1) / ((uint64_t)p->k * dstride);
+        g = gs < g ? gs : g;
+    }
+    return (uint32_t)(g < 1 ? 1 : g);
+}
+
+int rfec_wire_encode_send(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                          const uint8_t* shards, const rfec_hdr* hdr, const rfec_seg_stamp* seg_stamps,
+                          const uint32_t* seg_order, uint8_t* seg_dgram, uint16_t* seg_dlen,
+                          const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order, uint8_t* fec_dgram,
+                          uint16_t* fec_dlen, uint32_t dstride, void* stream)
+{
+    int rc = check_plan(plan, RFEC_MAX_K_ENCODE);
+    if (rc)
+        return rc;
+    const uint32_t k = plan->k, n = plan->n_lines;
+    if ((uint64_t)groups * k > 0xFFFFFFFFull || (uint64_t)groups * n > 0xFFFFFFFFull)
+        return set_err(RFEC_EINVAL, "groups * k or groups * n_lines overflows", 0);
+    const uint32_t ns = groups * k, nf = groups * n;
+    /* the SIM_FEC overhead covers the SIM_SEG's 36 */
+    if ((rc = check_wire(ns > nf ? ns : nf, stride, capacity, dstride, RFEC_WIRE_FEC_OVERHEAD)))
+        return rc;
+    if (dstride > WEF_MAX_DSTRIDE)
+        return set_err(RFEC_EINVAL,
+                       "rfec_wire_encode_send takes dstride <= 1280: use rfec_wire_frame_seg + rfec_wire_encode_fec",
+                       0);
+    if (groups == 0)
+        return RFEC_OK;
+    if (!shards || !hdr || !seg_stamps || !seg_dgram || !seg_dlen)
+        return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if (n && (!fec_stamps || !fec_dgram || !fec_dlen))
+        return set_err(RFEC_EINVAL, "NULL buffer (SIM_FEC)", 0);
+    if (misaligned(shards, 16) || misaligned(seg_dgram, 16) || (n && misaligned(fec_dgram, 16)))
+        return set_err(RFEC_EINVAL, "shards, seg_dgram and fec_dgram must be 16-byte aligned", 0);
+    if (misaligned(hdr, 4) || misaligned(seg_stamps, 4) || misaligned(seg_order, 4) ||
+        (n && (misaligned(fec_stamps, 4) || misaligned(fec_order, 4))))
+        return set_err(RFEC_EINVAL, "hdr, the stamps and the orders must be 4-byte aligned", 0);
+    if (misaligned(seg_dlen, 2) || (n && misaligned(fec_dlen, 2)))
+        return set_err(RFEC_EINVAL, "seg_dlen and fec_dlen must be 2-byte aligned", 0);
+    if (n == 0)
+        fec_order = NULL;
+    if (seg_order && (uint64_t)ns * dstride >= WEF_OFFSETS)
+        return set_err(RFEC_EINVAL, "with seg_order, the SIM_SEG slots must stay below 4 GiB", 0);
+    if (fec_order && (uint64_t)nf * dstride >= WEF_OFFSETS)
+        return set_err(RFEC_EINVAL, "with fec_order, the SIM_FEC slots must stay below 4 GiB", 0);
+    const uint32_t per = send_groups_per_launch(plan, stride, dstride, seg_order == NULL, fec_order == NULL);
+    for (uint32_t g0 = 0; g0 < groups; g0 += per) {
+        const uint32_t ng = groups - g0 < per ? groups - g0 : per;
+        const size_t r0 = (size_t)g0 * k, d0 = (size_t)g0 * n;
+        /* without an order a launch writes its own slots; with it, anywhere in the batch's */
+        const int e = rfec_launch_wire_encode_send(
+            plan, ng, stride, capacity, shards + r0 * stride, hdr + r0, seg_stamps + r0,
+            seg_order ? seg_order + r0 : NULL, seg_order ? seg_dgram : seg_dgram + r0 * dstride,
+            seg_order ? seg_dlen : seg_dlen + r0, seg_order ? ns : ng * k, n ? fec_stamps + d0 : NULL,
+            fec_order ? fec_order + d0 : NULL, fec_order || !n ? fec_dgram : fec_dgram + d0 * dstride,
+            fec_order || !n ? fec_dlen : fec_dlen + d0, fec_order ? nf : ng * n, dstride, stream);
+        if (e)
+            return set_err(RFEC_EDEVICE, "wire_encode_send launch", e);
     }
     return RFEC_OK;
 }

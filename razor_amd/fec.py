@@ -233,6 +233,8 @@ _SIGS = {
     "rfec_wire_frame_seg": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     "rfec_wire_encode_fec": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P,
                                        C.c_uint32, _P, _P, _P]),
+    "rfec_wire_encode_send": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P,
+                                        _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
     "rfec_wire_parse": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
@@ -469,6 +471,15 @@ class Native:
         self._check(self.lib.rfec_wire_encode_fec(C.byref(as_plan(plan)), groups, stride, capacity, shards, hdr,
                                                   stamps, order, dstride, dgram, dlen, stream),
                     "rfec_wire_encode_fec")
+
+    def wire_encode_send(self, plan, groups, stride, capacity, shards, hdr, seg_stamps, seg_dgram, seg_dlen,
+                         fec_stamps, fec_dgram, fec_dlen, dstride, stream=None, seg_order=None, fec_order=None):
+        """rfec_wire_encode_send: `groups` groups into their SIM_SEG and SIM_FEC datagrams, one kernel for
+        rfec_wire_frame_seg + rfec_wire_encode_fec (slots up to 1,280 bytes)."""
+        self._check(self.lib.rfec_wire_encode_send(C.byref(as_plan(plan)), groups, stride, capacity, shards, hdr,
+                                                   seg_stamps, seg_order, seg_dgram, seg_dlen, fec_stamps, fec_order,
+                                                   fec_dgram, fec_dlen, dstride, stream),
+                    "rfec_wire_encode_send")
 
     def wire_parse(self, n, dstride, dgram, dlen, stride, capacity, recs, payload, stream=None):
         self._check(self.lib.rfec_wire_parse(n, dstride, dgram, dlen, stride, capacity, recs, payload, stream),
