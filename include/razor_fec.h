@@ -187,7 +187,8 @@ int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec
  *    1 byte   status, out_index
  * (rfec_wire_encode_fec and rfec_wire_encode_send, the wire-codec calls that
  * check alignment: 16 bytes shards and the datagram slots, 4 bytes hdr, stamps
- * and orders, 2 bytes the lengths)
+ * and orders, 2 bytes the lengths; rfec_wire_regroup: the batch layout's as
+ * above, 16 bytes recs and payload, 4 bytes base_id, src_of and slot_of)
  *
  * Slot tails.  Every call works on the CD = ceil(capacity / 16) leading
  * 16-byte chunks of a slot (CD = 1 for capacity 0) and touches no byte of any
@@ -397,7 +398,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_parse) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_parse, rfec_wire_regroup) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -577,6 +578,89 @@ typedef struct {
 int rfec_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const uint16_t* dlen,
                     uint32_t stride, uint32_t capacity, rfec_wire_rec* recs, uint8_t* payload,
                     void* stream);
+
+/*
+ * Parsed datagrams into recover's batch layout, on the device: recs [n] and
+ * payload [n][stride] as rfec_wire_parse wrote them, in arrival order, placed
+ * into shards [G][k][stride], hdr, present, parity [G][n_l][stride], meta,
+ * fec_size and parity_present of rfec_encode_batch / rfec_recover_batch for
+ * `plan` and `groups` (k = plan->k, n_l = plan->n_lines).  For a receiver of
+ * groups of one shape: one call per shape, the records of other shapes and
+ * windows get ESHAPE / EWINDOW.  Group g has k + n_l slots: slot s < k is
+ * member s, slot k + l is parity line l.  All pointers are device pointers.
+ *
+ * One call is one closed window, and stateless: the timing rules of sim_fec.c
+ * -- the 3 s parity drop (:148), max_ts, eviction (:209-241) -- do not apply
+ * and are not modelled; nor is arrival order beyond "the first wins" (the
+ * reference delivers a segment recovered before its own late arrival; here
+ * that segment is present).  rfec_rx_recover and the receiver session replay
+ * those.
+ *
+ * The placement rule, independent of how the device schedules the work:
+ *  1. ENOTFEC.  A record with status != RFEC_WIRE_OK, or whose mid is neither
+ *     SIM_SEG nor SIM_FEC, gets ENOTFEC.
+ *  2. Group index.  fec_id == 0 gets EWINDOW.  Otherwise
+ *     g = fec_id >= fec_id0 ? fec_id - fec_id0 : fec_id + 65535 - fec_id0, the
+ *     sender's succession 65535 -> 1, skipping 0 (flex_fec_sender.c:241-243);
+ *     g >= groups gets EWINDOW.
+ *  3. Shape.  A SIM_FEC is shape-accepted when count == k, row == plan->row,
+ *     col == plan->col, index == plan->line[l].index for some l (the first
+ *     such l) and data_size <= capacity; otherwise it gets ESHAPE.
+ *  4. Anchor.  The group's anchor is its shape-accepted SIM_FEC with the
+ *     lowest arrival index; base_id[g] is the anchor's base_id (sim_fec.c:
+ *     152-163, flex_fec_receiver.c:69-78, :255-266).  With no anchor,
+ *     base_id[g] is 0.
+ *  5. Parity base.  A shape-accepted SIM_FEC whose base_id differs from
+ *     base_id[g] gets EBASE.  The others contend for slot k + l.
+ *  6. Segments.  A SIM_SEG in a group with no anchor gets ENOPARITY.
+ *     Otherwise i = (uint32_t)(hdr.seq - base_id[g]); i >= k gets EBASE;
+ *     otherwise the segment contends for slot i.
+ *  7. Winner.  The lowest arrival index wins a slot (first-arrival dedupe,
+ *     sim_fec.c:180-182, flex_fec_receiver.c:222-224, :258-260).  For the
+ *     winner d, slot_of[d] = g (k + n_l) + s.  Every other contender gets
+ *     EDUP.  src_of[g (k + n_l) + s] is the winner's arrival index, or
+ *     RFEC_REGROUP_NONE for an empty slot.
+ *
+ * Written: every element of slot_of [n] (the slot, or the negative code),
+ * src_of [G (k + n_l)], base_id [G], present [G][2] (bit i: member slot i is
+ * filled) and parity_present [G] (bit l: parity slot l is filled).  For each
+ * filled member slot, bytes [0, 16 CD) of its shards row, copied from the
+ * winner's payload row (CD: "Slot tails"), and hdr[g k + i] = rec.hdr; for each
+ * filled parity slot, bytes [0, 16 CD) of its parity row, meta = rec.hdr and
+ * fec_size = rec.data_size.  Nothing else: the rows and records of empty slots
+ * and bytes [16 CD, stride) of every row keep what they held, the inputs are
+ * untouched.  The outputs are then a complete input of rfec_recover_batch /
+ * rfec_recover_batch_out on the same buffers (recs, payload and src_of tell
+ * where every slot came from).
+ *
+ * Checked before any runtime call (RFEC_EINVAL): the plan (k <= RFEC_MAX_K),
+ * stride a multiple of 16 (at most 2,048, as rfec_wire_parse's),
+ * capacity <= stride, fec_id0 != 0, groups <= 65535, n <= 0x7FFFFFFF, NULL
+ * pointers, and alignment: 16 bytes recs, payload, shards, parity; 8 bytes
+ * present, parity_present; 4 bytes hdr, meta, base_id, src_of, slot_of; 2
+ * bytes fec_size.  groups == 0 touches nothing: every pointer may be NULL.
+ * n == 0 writes the masks (0), src_of (NONE) and base_id (0); recs, payload
+ * and slot_of may then be NULL.  n_lines == 0 is legal (parity, meta and
+ * fec_size may be NULL): no group has an anchor, so every candidate segment
+ * gets ENOPARITY.  The outputs must not overlap each other or the inputs (not
+ * checked).  The call allocates nothing, does not synchronise, launches only
+ * on `stream` and addresses rows with 64 bits (n * stride may pass 4 GiB).
+ * base_id holds intermediate values until the call's last kernel has run.
+ */
+#define RFEC_REGROUP_NONE      0xFFFFFFFFu
+#define RFEC_REGROUP_ENOTFEC   (-1)
+#define RFEC_REGROUP_EWINDOW   (-2)
+#define RFEC_REGROUP_ESHAPE    (-3)
+#define RFEC_REGROUP_ENOPARITY (-4)
+#define RFEC_REGROUP_EBASE     (-5)
+#define RFEC_REGROUP_EDUP      (-6)
+
+int rfec_wire_regroup(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0,
+                      uint32_t n, const rfec_wire_rec* recs, const uint8_t* payload,
+                      uint32_t stride, uint32_t capacity,
+                      uint8_t* shards, rfec_hdr* hdr, uint64_t* present,
+                      uint8_t* parity, rfec_hdr* meta, uint16_t* fec_size, uint64_t* parity_present,
+                      uint32_t* base_id, uint32_t* src_of, int32_t* slot_of, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Sender staging: sim_sender_put (sim_sender.c:306-377) with sim_split_frame */

@@ -16,7 +16,8 @@
  * rfec_hostmem.c (host-memory batches), rfec_sender.c (sender staging),
  * rfec_rx_*.c (receiver ingestion and sessions), rfec_packed_matrix.c (the
  * packed records of the row + column plans), rfec_wire_fused.c (the encode
- * and the SIM_FEC framing in one kernel).
+ * and the SIM_FEC framing in one kernel), rfec_wire_regroup.c (parsed
+ * datagrams into the batch layout).
  */
 #define _POSIX_C_SOURCE 200809L
 #ifndef __HIP_PLATFORM_AMD__

@@ -143,6 +143,14 @@ int rfec_launch_wire_encode_send(const rfec_kplan* P, uint32_t groups, uint32_t 
                                  uint32_t seg_rows_out, const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
                                  uint8_t* fec_dgram, uint16_t* fec_dlen, uint32_t fec_rows_out, uint32_t dstride,
                                  void* stream);
+/* rfec_wire_regroup (rfec_wire_regroup.c, kernels in rfec_regroup.hip): the call's four launches on `stream`.  The
+ * caller has checked the arguments (groups in [1, 65535], k <= RFEC_MAX_K, n < 2^31, stride a multiple of 16 up to
+ * 2,048, capacity <= stride, the pointers); hipErrorInvalidValue otherwise. */
+int rfec_launch_wire_regroup(const rfec_kplan* P, uint32_t groups, uint32_t fec_id0, uint32_t n,
+                             const rfec_wire_rec* recs, const uint8_t* payload, uint32_t stride, uint32_t capacity,
+                             uint8_t* shards, rfec_hdr* hdr, uint64_t* present, uint8_t* parity, rfec_hdr* meta,
+                             uint16_t* fec_size, uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
+                             int32_t* slot_of, void* stream);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */
 int rfec_launch_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const uint16_t* dlen,

@@ -1,0 +1,58 @@
+/*
+ * rfec_wire_regroup.c -- rfec_wire_regroup (razor_fec.h, wire codec): the
+ * parsed datagrams of one closed window, in arrival order, into the batch
+ * layout of rfec_recover_batch[_out] (rfec_regroup.hip): argument checks, all
+ * before any runtime call, then the launches through rfec_launch_wire_regroup.
+ *
+ * Not one of build.py's HOST_SRC: the CPU builds of the host layer link
+ * against a stub of the HIP runtime, which has no launch shims.
+ */
+#include "razor_fec.h"
+#include "rfec_internal.h"
+#include "rfec_host_internal.h"
+
+static int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+int rfec_wire_regroup(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0, uint32_t n,
+                      const rfec_wire_rec* recs, const uint8_t* payload, uint32_t stride, uint32_t capacity,
+                      uint8_t* shards, rfec_hdr* hdr, uint64_t* present, uint8_t* parity, rfec_hdr* meta,
+                      uint16_t* fec_size, uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
+                      int32_t* slot_of, void* stream)
+{
+    int rc = check_plan(plan, RFEC_MAX_K);
+    if (rc)
+        return rc;
+    /* rfec_wire_parse's geometry: rows of at most 2,048 bytes */
+    if (stride == 0 || stride % 16 || stride > RFEC_WIRE_MAX_DSTRIDE)
+        return set_err(RFEC_EINVAL, "stride must be a positive multiple of 16, at most 2048", 0);
+    if (capacity > stride)
+        return set_err(RFEC_EINVAL, "capacity must be <= stride", 0);
+    if (fec_id0 == 0)
+        return set_err(RFEC_EINVAL, "fec_id0 must not be 0 (the sender skips it)", 0);
+    if (groups > 65535u)
+        return set_err(RFEC_EINVAL, "groups must be <= 65535 (the fec_ids of one succession)", 0);
+    if (n > 0x7FFFFFFFu)
+        return set_err(RFEC_EINVAL, "n must be <= 0x7FFFFFFF", 0);
+    if (groups == 0)
+        return RFEC_OK;
+    const int nl = plan->n_lines;
+    if (!shards || !hdr || !present || !parity_present || !base_id || !src_of)
+        return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if (nl && (!parity || !meta || !fec_size))
+        return set_err(RFEC_EINVAL, "NULL buffer (parity, meta, fec_size)", 0);
+    if (n && (!recs || !payload || !slot_of))
+        return set_err(RFEC_EINVAL, "NULL buffer (recs, payload, slot_of)", 0);
+    if (misaligned(recs, 16) || misaligned(payload, 16) || misaligned(shards, 16) || misaligned(parity, 16))
+        return set_err(RFEC_EINVAL, "recs, payload, shards and parity must be 16-byte aligned", 0);
+    if (misaligned(present, 8) || misaligned(parity_present, 8))
+        return set_err(RFEC_EINVAL, "present and parity_present must be 8-byte aligned", 0);
+    if (misaligned(hdr, 4) || misaligned(meta, 4) || misaligned(base_id, 4) || misaligned(src_of, 4) ||
+        misaligned(slot_of, 4))
+        return set_err(RFEC_EINVAL, "hdr, meta, base_id, src_of and slot_of must be 4-byte aligned", 0);
+    if (misaligned(fec_size, 2))
+        return set_err(RFEC_EINVAL, "fec_size must be 2-byte aligned", 0);
+    const int e = rfec_launch_wire_regroup(plan, groups, fec_id0, n, recs, payload, stride, capacity, shards, hdr,
+                                           present, parity, meta, fec_size, parity_present, base_id, src_of, slot_of,
+                                           stream);
+    return e ? set_err(RFEC_EDEVICE, "wire_regroup launch", e) : RFEC_OK;
+}

@@ -236,6 +236,8 @@ _SIGS = {
     "rfec_wire_encode_send": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P,
                                         _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
     "rfec_wire_parse": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "rfec_wire_regroup": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint16, C.c_uint32, _P, _P, C.c_uint32,
+                                    C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "rfec_host_send_frames": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
@@ -484,6 +486,15 @@ class Native:
     def wire_parse(self, n, dstride, dgram, dlen, stride, capacity, recs, payload, stream=None):
         self._check(self.lib.rfec_wire_parse(n, dstride, dgram, dlen, stride, capacity, recs, payload, stream),
                     "rfec_wire_parse")
+
+    def wire_regroup(self, plan, groups, fec_id0, n, recs, payload, stride, capacity, shards, hdr, present, parity,
+                     meta, fec_size, parity_present, base_id, src_of, slot_of, stream=None):
+        """rfec_wire_regroup: n parsed datagrams (rfec_wire_parse's recs / payload, arrival order) of the window
+        of `groups` fec_ids from fec_id0 into the batch layout of rfec_recover_batch[_out]; base_id [G], src_of
+        [G (k + n_lines)] (u32) and slot_of [n] (i32) report the placement."""
+        self._check(self.lib.rfec_wire_regroup(C.byref(as_plan(plan)), groups, fec_id0, n, recs, payload, stride,
+                                               capacity, shards, hdr, present, parity, meta, fec_size, parity_present,
+                                               base_id, src_of, slot_of, stream), "rfec_wire_regroup")
 
     # -- sender staging (host memory) -------------------------------------------
     def sender_init(self):
