@@ -188,7 +188,9 @@ int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec
  * (rfec_wire_encode_fec and rfec_wire_encode_send, the wire-codec calls that
  * check alignment: 16 bytes shards and the datagram slots, 4 bytes hdr, stamps
  * and orders, 2 bytes the lengths; rfec_wire_regroup: the batch layout's as
- * above, 16 bytes recs and payload, 4 bytes base_id, src_of and slot_of)
+ * above, 16 bytes recs and payload, 4 bytes base_id, src_of and slot_of;
+ * rfec_wire_regroup_index and rfec_recover_indexed_out: the same, 16 bytes
+ * rows)
  *
  * Slot tails.  Every call works on the CD = ceil(capacity / 16) leading
  * 16-byte chunks of a slot (CD = 1 for capacity 0) and touches no byte of any
@@ -398,7 +400,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_parse, rfec_wire_regroup) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -661,6 +663,68 @@ int rfec_wire_regroup(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0,
                       uint8_t* shards, rfec_hdr* hdr, uint64_t* present,
                       uint8_t* parity, rfec_hdr* meta, uint16_t* fec_size, uint64_t* parity_present,
                       uint32_t* base_id, uint32_t* src_of, int32_t* slot_of, void* stream);
+
+/*
+ * rfec_wire_regroup without the row copy: the same records, the same placement
+ * rule (`capacity` is rule 3's bound) and the same four launches, and exactly
+ * what rfec_wire_regroup writes to hdr, present, meta, fec_size,
+ * parity_present, base_id, src_of and slot_of -- no payload row is read or
+ * written, so payload, stride, shards and parity are not arguments.  src_of is
+ * then the slot map of rfec_recover_indexed_out over rfec_wire_parse's payload
+ * rows where they lie.  The argument checks (no stride), the optional pointers
+ * (n == 0: recs, slot_of; n_lines == 0: meta, fec_size), groups == 0 and the
+ * guarantees (no allocation, no synchronisation, launches only on `stream`)
+ * are rfec_wire_regroup's.
+ */
+int rfec_wire_regroup_index(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0,
+                            uint32_t n, const rfec_wire_rec* recs, uint32_t capacity,
+                            rfec_hdr* hdr, uint64_t* present, rfec_hdr* meta, uint16_t* fec_size,
+                            uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
+                            int32_t* slot_of, void* stream);
+
+/*
+ * rfec_recover_batch_out with shards and parity replaced by a row pool and a
+ * slot map: rows [n_rows][stride], src_of [G (k + n_l)] u32; slot s < k of
+ * group g is member s, slot k + l is parity line l, and slot s of group g is
+ * row src_of[g (k + n_l) + s] of the pool.  This is the layout
+ * rfec_wire_regroup[_index] writes, though any producer may write it.  hdr,
+ * present, meta, fec_size and parity_present are the batch layout's.
+ *
+ * Consistency is the caller's to keep: a member or parity whose present /
+ * parity_present bit is set has src_of < n_rows.  The entries of absent slots
+ * are never read.  The kernels clamp a row index to n_rows - 1 before they use
+ * it: a broken map gives unspecified bytes for that group, never a read
+ * outside rows.
+ *
+ * Results: recovered, out_index, out_hdr, and out_shards over [0, 16 CD) of
+ * every slot whose out_index is not 0xFF, are byte for byte what
+ * rfec_recover_batch_out writes on the batch obtained by copying row
+ * src_of[slot] into each present slot -- for any plan with k <= RFEC_MAX_K,
+ * cascades included, and under every kernel selection (rfec_set_tuning).
+ * "Slot tails": bytes [16 CD, stride) of every out slot are not written and
+ * bytes [16 CD, stride) of the rows are not read; every input is untouched.
+ * Row addresses are 64-bit (n_rows * stride may pass 4 GiB).
+ *
+ * workspace: rfec_recover_workspace_size(plan, G) bytes, 16-byte aligned, as
+ * for rfec_recover_batch_out (row layouts of rows of <= 4 segments, k <= 64,
+ * run in one launch and leave it alone).
+ *
+ * Checked before any runtime call (RFEC_EINVAL, rfec_last_error names the
+ * argument): the plan, stride a positive multiple of 16, capacity <= stride,
+ * per_group in [1, k], groups * per_group * CD < 2^31, NULL pointers (rows may
+ * be NULL when n_rows == 0; meta and fec_size when n_lines == 0), and
+ * alignment: 16 bytes rows, out_shards and workspace; 8 bytes present,
+ * parity_present and recovered; 4 bytes src_of, hdr, meta and out_hdr; 2 bytes
+ * fec_size.  groups == 0 touches nothing: every pointer may be NULL.  The
+ * call allocates nothing, does not synchronise and launches only on `stream`.
+ */
+int rfec_recover_indexed_out(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                             const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of,
+                             const rfec_hdr* hdr, const uint64_t* present,
+                             const rfec_hdr* meta, const uint16_t* fec_size, const uint64_t* parity_present,
+                             uint64_t* recovered, uint32_t per_group,
+                             uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index,
+                             void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Sender staging: sim_sender_put (sim_sender.c:306-377) with sim_split_frame */

@@ -34,13 +34,15 @@ HIP_SRC = [CSRC / "rfec_kernels.hip", CSRC / "rfec_probe.hip", CSRC / "rfec_wire
 # rfec_rx_pool.c the replay threads, rfec_rx_plane.c the sharded plane and the host halves of compaction and of
 # the device tables, rfec_rx_dev.c the device side of ingestion, rfec_rx_session.c the sessions), and the flex
 # drop-in; rfec_packed_matrix.c (the packed matrix records' entry points) and rfec_wire_fused.c (the fused encode +
-# SIM_FEC framing's) and rfec_wire_regroup.c (parsed datagrams into the batch layout) call launch shims of their own,
+# SIM_FEC framing's), rfec_wire_regroup.c (parsed datagrams into the batch layout, and its index-only form) and
+# rfec_recover_indexed.c (the dense decode through a row map) call launch shims of their own,
 # so they stay out of HOST_SRC: the CPU builds of the host layer compile exactly HOST_SRC against a stub of the runtime
 HOST_NOHIP_SRC = ["rfec_rx_sim.c", "rfec_rx_pool.c", "rfec_rx_plane.c"]  # no GPU runtime: built and tested alone
 HOST_SRC = ["rfec_host.c", "rfec_dropin.c", "rfec_hostmem.c", "rfec_sender.c", *HOST_NOHIP_SRC, "rfec_rx_dev.c",
             "rfec_rx_session.c"]
 C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packed_matrix.c",
-                                          CSRC / "rfec_wire_fused.c", CSRC / "rfec_wire_regroup.c"]
+                                          CSRC / "rfec_wire_fused.c", CSRC / "rfec_wire_regroup.c",
+                                          CSRC / "rfec_recover_indexed.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h"]

@@ -151,6 +151,27 @@ int rfec_launch_wire_regroup(const rfec_kplan* P, uint32_t groups, uint32_t fec_
                              uint8_t* shards, rfec_hdr* hdr, uint64_t* present, uint8_t* parity, rfec_hdr* meta,
                              uint16_t* fec_size, uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
                              int32_t* slot_of, void* stream);
+/* rfec_wire_regroup_index (rfec_wire_regroup.c): the same four launches, k_regroup_place with no row lane; the
+ * caller has checked the same arguments but for the stride. */
+int rfec_launch_wire_regroup_index(const rfec_kplan* P, uint32_t groups, uint32_t fec_id0, uint32_t n,
+                                   const rfec_wire_rec* recs, uint32_t capacity, rfec_hdr* hdr, uint64_t* present,
+                                   rfec_hdr* meta, uint16_t* fec_size, uint64_t* parity_present, uint32_t* base_id,
+                                   uint32_t* src_of, int32_t* slot_of, void* stream);
+/* rfec_recover_indexed_out (rfec_recover_indexed.c, kernels in rfec_kernels.hip): the dense decode with member and
+ * parity rows read from rows [n_rows][stride] through src_of [G (k + n_lines)].  The caller has checked the plan
+ * (k <= RFEC_MAX_K), stride a multiple of 16, capacity <= stride, out->per_group in [1, k],
+ * groups * per_group * CD < 2^31, groups << ceil(log2 n_lines) < 2^32 and the pointers; hipErrorInvalidValue
+ * otherwise.  flags: RFEC_KFLAG_GENERIC sends a row layout down the peel + replay too. */
+int rfec_launch_recover_indexed(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of, const rfec_hdr* hdr,
+                                const uint64_t* present, const rfec_hdr* meta, const uint16_t* fsize,
+                                const uint64_t* parity_present, uint64_t* recovered, void* ws, void* stream,
+                                unsigned flags, const rfec_dense_out* out);
+/* Which kernels the calling thread's last rfec_launch_recover_indexed took (host-side, thread-local, for tests;
+ * apart from rfec_last_path, whose kinds are a closed table): 0 none yet, 1 | K << 8 one launch of
+ * k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8 k_peel_lds +
+ * k_recover_indexed<MAXC, ...> (MAXC = 4, 8). */
+uint32_t rfec_indexed_last_path(void);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */
 int rfec_launch_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const uint16_t* dlen,

@@ -34,6 +34,9 @@
 //      checks of the steps it depends on and recomputes them in registers;
 //    * otherwise (and RFEC_TUNE_GENERIC): k_peel_lds (schedule records) +
 //      k_recover_flat (replay).
+//  recover through a slot map over a row pool (rfec_launch_recover_indexed,
+//  dense output only): row layouts in one launch of k_decode_rows_indexed,
+//  every other plan k_peel_lds + k_recover_indexed.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -786,6 +789,104 @@ __global__ __launch_bounds__(kBlock) void k_recover_flat(v4u* shards, const v4u*
     const uint64_t h0 = D.E ? present[2 * g] : 0ull, h1 = D.E ? present[2 * g + 1] : 0ull;
     replay<MAXC, BATCH>(shards + (size_t)g * P.k * C + j, parity + (size_t)g * P.n_lines * C + j, rec, r0, C,
                         fast_ok, lplan, out, h0, h1);
+}
+
+// The replay of rfec_recover_indexed_out: k_recover_flat's, dense output only, with member i of the group read
+// from row so[i] of the pool and parity line l from row so[K + l] (so: the group's K + NL words of src_of, rows:
+// chunk j of row 0).  A row index is clamped to `last` = n_rows - 1 before it is used, so a broken map reads
+// other rows, never past the pool; row addresses are 64-bit.  Only the entries of slots a step reads are loaded
+// (present members and received parities); a step reads an earlier step's result from the dense out slot.
+__device__ __forceinline__ const v4u* pool_row(const v4u* rows, const uint32_t* __restrict__ so, uint32_t slot,
+                                               uint32_t last, uint32_t C)
+{
+    return rows + (size_t)min(so[slot], last) * C;
+}
+
+template <int MAXC, int BATCH>
+__device__ __forceinline__ void replay_indexed(const v4u* rows, const uint32_t* __restrict__ so, uint32_t K,
+                                               uint32_t last, const uint8_t* __restrict__ rec, const v4u r0,
+                                               uint32_t C, uint32_t fast_ok, const uint32_t* lplan, v4u* out,
+                                               uint64_t h0, uint64_t h1)
+{
+    const uint32_t n = rec_byte(r0, 0);
+    uint32_t s = 0;
+    if (fast_ok && rec_byte(r0, 1)) {
+        const uint32_t nf = n < 7 ? n : 7;
+        for (; s < nf; s += BATCH) {
+            // (unconditional loads: the map words of a batch first, then its rows; an unused member and an off
+            // step re-read a parity chunk of the batch)
+            v4u acc[BATCH], mv[BATCH][MAXC];
+            const v4u* src[BATCH][MAXC + 1];
+            uint32_t tg[BATCH], l0 = 0;
+            bool on[BATCH], use[BATCH][MAXC];
+#pragma unroll
+            for (int b = 0; b < BATCH; ++b) {
+                on[b] = s + b < nf;
+                const uint32_t l = on[b] ? rec_byte(r0, 2 + 2 * (s + b)) : l0;
+                l0 = l;
+                tg[b] = rec_byte(r0, 3 + 2 * (s + b));
+                const uint32_t ln = lplan[l];
+                const uint32_t first = ln & 0xff, stride = (ln >> 8) & 0xff, count = (ln >> 16) & 0xff;
+                src[b][MAXC] = pool_row(rows, so, K + l, last, C);
+#pragma unroll
+                for (int q = 0; q < MAXC; ++q) {
+                    const uint32_t i = first + q * stride;
+                    use[b][q] = on[b] && (uint32_t)q < count && i != tg[b];
+                    src[b][q] = pool_row(rows, so, use[b][q] ? i : K + l, last, C);
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < BATCH; ++b) {
+                acc[b] = ld16(src[b][MAXC]);
+#pragma unroll
+                for (int q = 0; q < MAXC; ++q)
+                    mv[b][q] = ld16(src[b][q]);
+            }
+#pragma unroll
+            for (int b = 0; b < BATCH; ++b) {
+#pragma unroll
+                for (int q = 0; q < MAXC; ++q)
+                    acc[b] ^= use[b][q] ? mv[b][q] : v4u{0, 0, 0, 0};
+                if (on[b])
+                    st16(out + (size_t)missing_rank(h0, h1, tg[b]) * C, acc[b]);
+            }
+        }
+        s = nf;
+    }
+    for (; s < n; ++s) {
+        const uint32_t l = s < 7 ? rec_byte(r0, 2 + 2 * s) : rec[2 + 2 * s];
+        const uint32_t tt = s < 7 ? rec_byte(r0, 3 + 2 * s) : rec[3 + 2 * s];
+        const uint32_t ln = lplan[l];
+        const uint32_t first = ln & 0xff, stride = (ln >> 8) & 0xff, count = (ln >> 16) & 0xff;
+        v4u acc = ld16(pool_row(rows, so, K + l, last, C));
+        for (uint32_t q = 0; q < count; ++q) {
+            const uint32_t i = first + q * stride;
+            if (i != tt)
+                acc ^= !has_bit(h0, h1, i) ? out[(size_t)missing_rank(h0, h1, i) * C] : *pool_row(rows, so, i, last, C);
+        }
+        st16(out + (size_t)missing_rank(h0, h1, tt) * C, acc);
+    }
+}
+
+template <int MAXC, int BATCH>
+__global__ __launch_bounds__(kBlock) void k_recover_indexed(const v4u* rows, uint32_t last,
+                                                            const uint32_t* __restrict__ src_of,
+                                                            const uint8_t* __restrict__ sched, uint32_t total,
+                                                            uint32_t C, FastDiv divC, uint32_t rec_bytes,
+                                                            uint32_t fast_ok, rfec_kplan P, DenseOut D,
+                                                            const uint64_t* __restrict__ present)
+{
+    __shared__ uint32_t lplan[RFEC_MAX_LINES];
+    stage_plan(lplan, P);
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= total)
+        return;
+    const uint32_t g = fdiv(t, divC);
+    const uint32_t j = t - g * divC.d; // chunk column (divC.d = chunks of work per slot)
+    const uint8_t* rec = sched + (size_t)g * rec_bytes;
+    const v4u r0 = *reinterpret_cast<const v4u*>(rec);
+    replay_indexed<MAXC, BATCH>(rows + j, src_of + (size_t)g * (P.k + P.n_lines), P.k, last, rec, r0, C, fast_ok,
+                                lplan, D.sh + (size_t)g * D.E * C + j, present[2 * g], present[2 * g + 1]);
 }
 
 // ---------------------------------------------------------------------------
@@ -2132,6 +2233,69 @@ __global__ __launch_bounds__(kBlock) void k_decode_rows(v4u* shards, const v4u* 
     st16(dst, acc);
 }
 
+// k_decode_rows<K, COL, SLOTS = true> for rfec_recover_indexed_out: the same grid, header blocks and lanes per
+// (group, output slot, chunk), with the row's parity chunk read from row src_of[g (KK + R) + KK + r] of the pool
+// and member i from row src_of[g (KK + R) + i].  The rows lie anywhere in the pool, so no descriptor spans a
+// wave's loads: they are plain 64-bit addresses, the map words loaded first, then the parity and the COL member
+// chunks unconditionally and in flight together; a member that is not wanted (past the row's end, or the
+// target) re-reads the parity chunk, as in k_decode_out, and only wanted slots' map words are read.  A row index
+// is clamped to `last` = n_rows - 1 before it is used.
+template <int K, int COL>
+__global__ __launch_bounds__(kBlock) void k_decode_rows_indexed(const v4u* rows, uint32_t last,
+                                                                const uint32_t* __restrict__ src_of, uint32_t total,
+                                                                uint32_t C, FastDiv divC, FastDiv divRC,
+                                                                uint32_t n_hdr_blocks, uint32_t hdr_every, PeelArgs A,
+                                                                rfec_kmask M, DenseOut D, uint32_t npay8,
+                                                                uint32_t k_rt, uint32_t col_rt, FastDiv divCol)
+{
+    static_assert(K <= 64, "row decode keeps the present mask in one word");
+    const uint32_t KK = K ? (uint32_t)K : k_rt, CC = K ? (uint32_t)COL : col_rt;
+    uint32_t hb, pb;
+    if (header_block_xcd((n_hdr_blocks + 7u) >> 3, hdr_every, npay8, &hb, &pb)) {
+        if (hb < n_hdr_blocks)
+            line_headers(A, M, hb);
+        return;
+    }
+    const uint32_t R = (KK + CC - 1) / CC, LAST = KK - (R - 1) * CC;
+    const uint32_t t = pb * kBlock + threadIdx.x;
+    if (t >= total)
+        return;
+    const uint32_t g = fdiv(t, divRC);
+    const uint32_t rem = t - g * divRC.d;
+    const uint32_t q0 = fdiv(rem, divC); // output slot
+    const uint32_t j = rem - q0 * divC.d;
+    const uint64_t h = A.present[2 * g];
+    uint64_t m = ~h & (KK == 64 ? ~0ull : (1ull << KK) - 1ull);
+    for (uint32_t u = 0; u < q0; ++u) // the q0-th erased segment
+        m &= m - 1ull;
+    if (!m)
+        return;
+    const uint32_t tgt = (uint32_t)__ffsll((long long)m) - 1;
+    const uint32_t r = K ? tgt / (uint32_t)COL : fdiv(tgt, divCol);
+    const uint32_t cnt = r + 1 < R ? CC : LAST;
+    const uint64_t rm = ((1ull << cnt) - 1ull) << (r * CC);
+    if (__popcll(rm & ~h) != 1 || !((A.parity_present[g] >> r) & 1ull))
+        return;
+    const uint32_t* so = src_of + (size_t)g * (KK + R);
+    const v4u* src[COL + 1];
+    bool use[COL];
+    src[COL] = pool_row(rows, so, KK + r, last, C) + j;
+#pragma unroll
+    for (int q = 0; q < COL; ++q) {
+        use[q] = (uint32_t)q < cnt && r * CC + q != tgt;
+        src[q] = pool_row(rows, so, use[q] ? r * CC + q : KK + r, last, C) + j;
+    }
+    v4u acc = ld16(src[COL]);
+    v4u mv[COL];
+#pragma unroll
+    for (int q = 0; q < COL; ++q)
+        mv[q] = ld16(src[q]);
+#pragma unroll
+    for (int q = 0; q < COL; ++q)
+        acc ^= use[q] ? mv[q] : v4u{0, 0, 0, 0};
+    st16(D.sh + ((size_t)g * D.E + q0) * C + j, acc);
+}
+
 // The batch layout -> packed erasure records (rfec_pack_erasures): one lane
 // per (group, output slot e), 2^lg >= E lanes per group.  Slot e: the fec_meta
 // and fec_data_size of the row of the group's e-th erased segment and the
@@ -2788,6 +2952,108 @@ int launch_recover(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32
 }
 
 } // namespace
+
+// rfec_recover_indexed_out's dispatch tag (rfec_internal.h), kept apart from t_path's kinds
+static thread_local uint32_t t_indexed_path = 0;
+
+extern "C" uint32_t rfec_indexed_last_path(void) { return t_indexed_path; }
+
+// rfec_recover_indexed_out (rfec_recover_indexed.c): rfec_recover_batch_out's dense decode with every member and
+// parity row read through src_of from the pool `rows` [n_rows][stride].  Row layouts (rows of <= 4, k <= 64): one
+// launch of k_decode_rows_indexed, no workspace.  Any other plan, and RFEC_KFLAG_GENERIC: k_peel_lds in dense mode
+// (it reads the tables only), then k_recover_indexed.  n_rows == 0 (no slot can be present): the peel alone.
+extern "C" int rfec_launch_recover_indexed(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                           const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of,
+                                           const rfec_hdr* hdr, const uint64_t* present, const rfec_hdr* meta,
+                                           const uint16_t* fsize, const uint64_t* parity_present,
+                                           uint64_t* recovered, void* ws, void* stream, unsigned flags,
+                                           const rfec_dense_out* out)
+{
+    const rfec_kplan& P = M->plan;
+    const uint32_t C = stride / 16, cd = capacity ? (capacity + 15) / 16 : 1, E = out ? out->per_group : 0;
+    uint32_t lg = 1;
+    while ((1u << lg) < P.n_lines)
+        ++lg;
+    if (!groups || !stride || stride % 16 || capacity > stride || !P.k || P.k > RFEC_MAX_K ||
+        P.n_lines > RFEC_MAX_LINES || !E || E > P.k || (uint64_t)groups * E * cd >= (1ull << 31) ||
+        ((uint64_t)groups << lg) >= (1ull << 32))
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    PeelArgs B;
+    B.hdr = const_cast<rfec_hdr*>(hdr); // dense output: the header lanes and the peel only read it
+    B.present = present;
+    B.meta = meta;
+    B.fsize = fsize;
+    B.parity_present = parity_present;
+    B.recovered = recovered;
+    B.sched = reinterpret_cast<uint8_t*>(ws);
+    B.groups = groups;
+    B.capacity = capacity;
+    B.rec_bytes = rfec_sched_record_bytes(P.k, P.n_lines);
+    B.out_hdr = out->hdr;
+    B.out_index = out->index;
+    B.out_per_group = E;
+    B.packed = nullptr;
+    B.pk_stride = B.pk_slot = 0;
+    B.nlp_log2 = 0;
+    B.disjoint = 1;
+    uint64_t seen0 = 0, seen1 = 0;
+    uint32_t maxc = 0;
+    for (uint32_t l = 0; l < P.n_lines; ++l) {
+        if ((seen0 & M->mask[l][0]) | (seen1 & M->mask[l][1]))
+            B.disjoint = 0;
+        seen0 |= M->mask[l][0];
+        seen1 |= M->mask[l][1];
+        maxc = P.line[l].count > maxc ? P.line[l].count : maxc;
+    }
+    const v4u* pool = reinterpret_cast<const v4u*>(rows);
+    const uint32_t last = n_rows ? n_rows - 1 : 0;
+    const DenseOut DO = {reinterpret_cast<v4u*>(out->shards), E};
+    const FastDiv dC = make_fastdiv(cd);
+    uint32_t col = 0;
+    if (n_rows && !(flags & RFEC_KFLAG_GENERIC) && is_row_layout(&P, &col) && col <= 4 && P.k <= 64) {
+        // launch_fused_rows' grid: header lanes per (group, line), payload lanes per (group, out slot, chunk)
+        B.gpb = 1;
+        B.nlp_log2 = lg;
+        const uint32_t n_hdr = (uint32_t)((((uint64_t)groups << lg) + kBlock - 1) / kBlock);
+        const uint32_t total = groups * E * cd;
+        const uint32_t npay8 = (blocks_for(total) + 7u) & ~7u, nhr = (n_hdr + 7u) >> 3;
+        const dim3 grid(8u * nhr + npay8);
+        const uint32_t every = nhr ? (npay8 >> 3) / nhr : 0u;
+        const FastDiv dRC = make_fastdiv(E * cd), dCol = make_fastdiv(col);
+        const uint32_t kt = col == 4 && (P.k == 10 || P.k == 32) ? P.k : 0u;
+        t_indexed_path = 1u | kt << 8;
+        if (kt == 10)
+            RFEC_LAUNCH((k_decode_rows_indexed<10, 4>), grid, dim3(kBlock), 0, st, pool, last, src_of, total, C, dC,
+                        dRC, n_hdr, every, B, *M, DO, npay8, P.k, col, dCol);
+        else if (kt == 32)
+            RFEC_LAUNCH((k_decode_rows_indexed<32, 4>), grid, dim3(kBlock), 0, st, pool, last, src_of, total, C, dC,
+                        dRC, n_hdr, every, B, *M, DO, npay8, P.k, col, dCol);
+        else
+            RFEC_LAUNCH((k_decode_rows_indexed<0, 4>), grid, dim3(kBlock), 0, st, pool, last, src_of, total, C, dC,
+                        dRC, n_hdr, every, B, *M, DO, npay8, P.k, col, dCol);
+        return (int)hipGetLastError();
+    }
+    // the peel's blocks as launch_recover sizes them
+    uint32_t gpb = (kPeelDwords - 8) / (5u * P.k + 6u * P.n_lines);
+    gpb = gpb > 64u ? 64u : gpb;
+    if (gpb >= 8)
+        gpb &= ~7u;
+    B.gpb = gpb < 1 ? 1 : gpb;
+    t_indexed_path = 2u | (maxc <= 4 ? 4u : 8u) << 8;
+    RFEC_LAUNCH(k_peel_lds, dim3((groups + B.gpb - 1) / B.gpb), dim3(kBlock), 0, st, B, *M);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !n_rows)
+        return (int)e;
+    const uint32_t total = groups * cd, fast = maxc <= 8 ? 1u : 0u;
+    if (maxc <= 4)
+        RFEC_LAUNCH((k_recover_indexed<4, 2>), dim3(blocks_for(total)), dim3(kBlock), 0, st, pool, last, src_of,
+                    B.sched, total, C, dC, B.rec_bytes, fast, P, DO, present);
+    else
+        RFEC_LAUNCH((k_recover_indexed<8, 1>), dim3(blocks_for(total)), dim3(kBlock), 0, st, pool, last, src_of,
+                    B.sched, total, C, dC, B.rec_bytes, fast, P, DO, present);
+    return (int)hipGetLastError();
+}
 
 extern "C" {
 

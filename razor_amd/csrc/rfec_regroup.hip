@@ -24,6 +24,8 @@
 //                      (1-4 % of the call), a lane per slot writes hdr / meta / fec_size from the winner's record,
 //                      a lane per group the two masks and base_id, a lane per record turns a beaten contender's
 //                      slot_of into EDUP
+// rfec_wire_regroup_index is the same call without the row lanes: the tables alone, src_of then being the row map
+// of rfec_recover_indexed_out.
 // The rows are loaded non-temporally (each is read once) and stored with the default policy: the decode reads
 // them next.  Row and record addresses are 64-bit (records x stride passes 4 GiB on the large shapes).
 #include <hip/hip_runtime.h>
@@ -268,19 +270,21 @@ __global__ __launch_bounds__(kBlock) void k_regroup_place(const RgArgs A, const 
 // The caller (rfec_wire_regroup.c) has checked the plan (k <= RFEC_MAX_K), groups in [1, 65535], n < 2^31, stride a
 // multiple of 16, capacity <= stride and the pointers.  Lane counts: G (k + n_lines) CD < 65535 * 192 * 128 < 2^31
 // (the dividends of the fast divisions), and with the slots', the groups' and the records' lanes below 2^32.
-extern "C" int rfec_launch_wire_regroup(const rfec_kplan* P, uint32_t groups, uint32_t fec_id0, uint32_t n,
-                                        const rfec_wire_rec* recs, const uint8_t* payload, uint32_t stride,
-                                        uint32_t capacity, uint8_t* shards, rfec_hdr* hdr, uint64_t* present,
-                                        uint8_t* parity, rfec_hdr* meta, uint16_t* fec_size,
-                                        uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
-                                        int32_t* slot_of, void* stream)
+//
+// copy_rows false (rfec_wire_regroup_index): the same four launches with no (slot, chunk) lane in k_regroup_place's
+// grid, so no payload row is read or written (payload, shards, parity and stride are not used).
+static int launch_regroup(const rfec_kplan* P, uint32_t groups, uint32_t fec_id0, uint32_t n,
+                          const rfec_wire_rec* recs, const uint8_t* payload, uint32_t stride, uint32_t capacity,
+                          uint8_t* shards, rfec_hdr* hdr, uint64_t* present, uint8_t* parity, rfec_hdr* meta,
+                          uint16_t* fec_size, uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
+                          int32_t* slot_of, void* stream, bool copy_rows)
 {
     const uint32_t k = P->k, nl = P->n_lines, slots = k + nl;
-    if (!groups || groups > 65535u || !k || k > RFEC_MAX_K || nl > RFEC_MAX_LINES || n > 0x7FFFFFFFu || !stride ||
-        stride % 16 || capacity > stride || stride > 16u * 128u)
+    if (!groups || groups > 65535u || !k || k > RFEC_MAX_K || nl > RFEC_MAX_LINES || n > 0x7FFFFFFFu ||
+        (copy_rows && (!stride || stride % 16 || capacity > stride || stride > 16u * 128u)))
         return (int)hipErrorInvalidValue;
     const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const uint32_t C = stride / 16, CD = capacity ? (capacity + 15) / 16 : 1;
+    const uint32_t C = stride / 16, CD = copy_rows && capacity ? (capacity + 15) / 16 : 1;
     RgArgs A;
     A.recs = recs;
     A.n = n;
@@ -315,10 +319,31 @@ extern "C" int rfec_launch_wire_regroup(const rfec_kplan* P, uint32_t groups, ui
     Q.C = C;
     Q.CD = CD;
     Q.n_slots = n_slots;
-    Q.n_rows = n_slots * CD;
+    Q.n_rows = copy_rows ? n_slots * CD : 0u;
     Q.divCD = make_fastdiv(CD);
     Q.divSlots = make_fastdiv(slots);
     RFEC_LAUNCH(k_regroup_place, dim3(blocks_for((uint64_t)Q.n_rows + n_slots + groups + n)), dim3(kBlock), 0, st, A,
                 Q);
     return (int)hipGetLastError();
+}
+
+extern "C" int rfec_launch_wire_regroup(const rfec_kplan* P, uint32_t groups, uint32_t fec_id0, uint32_t n,
+                                        const rfec_wire_rec* recs, const uint8_t* payload, uint32_t stride,
+                                        uint32_t capacity, uint8_t* shards, rfec_hdr* hdr, uint64_t* present,
+                                        uint8_t* parity, rfec_hdr* meta, uint16_t* fec_size,
+                                        uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
+                                        int32_t* slot_of, void* stream)
+{
+    return launch_regroup(P, groups, fec_id0, n, recs, payload, stride, capacity, shards, hdr, present, parity, meta,
+                          fec_size, parity_present, base_id, src_of, slot_of, stream, true);
+}
+
+extern "C" int rfec_launch_wire_regroup_index(const rfec_kplan* P, uint32_t groups, uint32_t fec_id0, uint32_t n,
+                                              const rfec_wire_rec* recs, uint32_t capacity, rfec_hdr* hdr,
+                                              uint64_t* present, rfec_hdr* meta, uint16_t* fec_size,
+                                              uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
+                                              int32_t* slot_of, void* stream)
+{
+    return launch_regroup(P, groups, fec_id0, n, recs, nullptr, 0, capacity, nullptr, hdr, present, nullptr, meta,
+                          fec_size, parity_present, base_id, src_of, slot_of, stream, false);
 }

@@ -56,3 +56,41 @@ int rfec_wire_regroup(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0, 
                                            stream);
     return e ? set_err(RFEC_EDEVICE, "wire_regroup launch", e) : RFEC_OK;
 }
+
+/* rfec_wire_regroup without the row copy: the tables alone (src_of is the row map of rfec_recover_indexed_out) */
+int rfec_wire_regroup_index(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0, uint32_t n,
+                            const rfec_wire_rec* recs, uint32_t capacity, rfec_hdr* hdr, uint64_t* present,
+                            rfec_hdr* meta, uint16_t* fec_size, uint64_t* parity_present, uint32_t* base_id,
+                            uint32_t* src_of, int32_t* slot_of, void* stream)
+{
+    int rc = check_plan(plan, RFEC_MAX_K);
+    if (rc)
+        return rc;
+    if (fec_id0 == 0)
+        return set_err(RFEC_EINVAL, "fec_id0 must not be 0 (the sender skips it)", 0);
+    if (groups > 65535u)
+        return set_err(RFEC_EINVAL, "groups must be <= 65535 (the fec_ids of one succession)", 0);
+    if (n > 0x7FFFFFFFu)
+        return set_err(RFEC_EINVAL, "n must be <= 0x7FFFFFFF", 0);
+    if (groups == 0)
+        return RFEC_OK;
+    const int nl = plan->n_lines;
+    if (!hdr || !present || !parity_present || !base_id || !src_of)
+        return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if (nl && (!meta || !fec_size))
+        return set_err(RFEC_EINVAL, "NULL buffer (meta, fec_size)", 0);
+    if (n && (!recs || !slot_of))
+        return set_err(RFEC_EINVAL, "NULL buffer (recs, slot_of)", 0);
+    if (misaligned(recs, 16))
+        return set_err(RFEC_EINVAL, "recs must be 16-byte aligned", 0);
+    if (misaligned(present, 8) || misaligned(parity_present, 8))
+        return set_err(RFEC_EINVAL, "present and parity_present must be 8-byte aligned", 0);
+    if (misaligned(hdr, 4) || misaligned(meta, 4) || misaligned(base_id, 4) || misaligned(src_of, 4) ||
+        misaligned(slot_of, 4))
+        return set_err(RFEC_EINVAL, "hdr, meta, base_id, src_of and slot_of must be 4-byte aligned", 0);
+    if (misaligned(fec_size, 2))
+        return set_err(RFEC_EINVAL, "fec_size must be 2-byte aligned", 0);
+    const int e = rfec_launch_wire_regroup_index(plan, groups, fec_id0, n, recs, capacity, hdr, present, meta,
+                                                 fec_size, parity_present, base_id, src_of, slot_of, stream);
+    return e ? set_err(RFEC_EDEVICE, "wire_regroup_index launch", e) : RFEC_OK;
+}

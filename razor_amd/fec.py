@@ -238,6 +238,10 @@ _SIGS = {
     "rfec_wire_parse": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "rfec_wire_regroup": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint16, C.c_uint32, _P, _P, C.c_uint32,
                                     C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rfec_wire_regroup_index": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint16, C.c_uint32, _P, C.c_uint32,
+                                          _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rfec_recover_indexed_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32,
+                                           _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "rfec_host_send_frames": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
@@ -495,6 +499,24 @@ class Native:
         self._check(self.lib.rfec_wire_regroup(C.byref(as_plan(plan)), groups, fec_id0, n, recs, payload, stride,
                                                capacity, shards, hdr, present, parity, meta, fec_size, parity_present,
                                                base_id, src_of, slot_of, stream), "rfec_wire_regroup")
+
+    def wire_regroup_index(self, plan, groups, fec_id0, n, recs, capacity, hdr, present, meta, fec_size,
+                           parity_present, base_id, src_of, slot_of, stream=None):
+        """rfec_wire_regroup_index: rfec_wire_regroup's tables without the row copy; src_of is then the row map
+        of recover_indexed_out over rfec_wire_parse's payload rows."""
+        self._check(self.lib.rfec_wire_regroup_index(C.byref(as_plan(plan)), groups, fec_id0, n, recs, capacity, hdr,
+                                                     present, meta, fec_size, parity_present, base_id, src_of,
+                                                     slot_of, stream), "rfec_wire_regroup_index")
+
+    def recover_indexed_out(self, plan, groups, stride, capacity, rows, n_rows, src_of, hdr, present, meta, fec_size,
+                            parity_present, recovered, per_group, out_shards, out_hdr, out_index, workspace,
+                            stream=None):
+        """rfec_recover_indexed_out: recover_batch_out with slot s of group g read from row
+        src_of[g (k + n_lines) + s] of rows [n_rows][stride]."""
+        self._check(self.lib.rfec_recover_indexed_out(C.byref(as_plan(plan)), groups, stride, capacity, rows, n_rows,
+                                                      src_of, hdr, present, meta, fec_size, parity_present, recovered,
+                                                      per_group, out_shards, out_hdr, out_index, workspace, stream),
+                    "rfec_recover_indexed_out")
 
     # -- sender staging (host memory) -------------------------------------------
     def sender_init(self):
