@@ -190,7 +190,8 @@ int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec
  * and orders, 2 bytes the lengths; rfec_wire_regroup: the batch layout's as
  * above, 16 bytes recs and payload, 4 bytes base_id, src_of and slot_of;
  * rfec_wire_regroup_index and rfec_recover_indexed_out: the same, 16 bytes
- * rows)
+ * rows; rfec_wire_regroup_shapes: the same per section, 4 bytes group_of,
+ * rank_of, anchor_of and counts)
  *
  * Slot tails.  Every call works on the CD = ceil(capacity / 16) leading
  * 16-byte chunks of a slot (CD = 1 for capacity 0) and touches no byte of any
@@ -681,6 +682,108 @@ int rfec_wire_regroup_index(const rfec_plan* plan, uint32_t groups, uint16_t fec
                             rfec_hdr* hdr, uint64_t* present, rfec_hdr* meta, uint16_t* fec_size,
                             uint64_t* parity_present, uint32_t* base_id, uint32_t* src_of,
                             int32_t* slot_of, void* stream);
+
+/*
+ * rfec_wire_regroup_index for a window whose groups have different shapes: the
+ * flex sender closes a group per frame, so k, and with it row x col
+ * (rfec_num_packets), follows the frame size.  One call classifies every group
+ * of the closed window by the shape of its first accepted parity, the rule by
+ * which the reference creates a flex (sim_fec.c:152-163,
+ * flex_fec_receiver.c:69-78), compacts the groups of each shape in window order
+ * and writes, per shape, one dense section of exactly the tables
+ * rfec_recover_indexed_out reads.  plans [n_plans] and sections [n_plans] are
+ * host arrays (sections: of device pointers), section p belonging to plans[p]
+ * (k_p = plans[p].k, n_p = plans[p].n_lines); everything else is a device
+ * pointer.  More than RFEC_REGROUP_MAX_SHAPES shapes need more than one call
+ * over the window.
+ *
+ * The rule, independent of how the device schedules the work:
+ *  1. ENOTFEC, EWINDOW.  Rules 1 and 2 of rfec_wire_regroup, unchanged: the
+ *     group index g counts from fec_id0 in the succession 65535 -> 1, and
+ *     fec_id == 0 gets EWINDOW.
+ *  2. Shape.  A SIM_FEC is accepted by plan p when count == plans[p].k, row and
+ *     col equal the plan's, index == plans[p].line[l].index for some l (the
+ *     first such l) and data_size <= capacity.  The plans of one call differ
+ *     pairwise in (k, row, col), so at most one p accepts a record.  A SIM_FEC
+ *     accepted by no plan gets ESHAPE.
+ *  3. Anchor and shape of a group.  anchor_of[g] is the lowest arrival index
+ *     among the accepted SIM_FECs of group g, of any plan, or
+ *     RFEC_REGROUP_NONE.  shape_of[g] is the plan that accepts the anchor, or
+ *     0xFF.  The group's base_id is the anchor's.  A SIM_FEC accepted by a plan
+ *     other than shape_of[g] gets ESHAPE: the reference's flex keeps the
+ *     geometry of its first parity.
+ *  4. Rank.  rank_of[g] is the number of g' < g with shape_of[g'] ==
+ *     shape_of[g] -- window order, not arrival order -- or RFEC_REGROUP_NONE
+ *     for a group with no anchor.  counts[p] is the number of groups of shape
+ *     p in the window; it is not clamped to cap.
+ *  5. Parity base and segments.  Rules 5 and 6 of rfec_wire_regroup with k and
+ *     the lines of plans[shape_of[g]]: EBASE, ENOPARITY, and the slot s (member
+ *     i: s = i; parity line l: s = k_p + l).
+ *  6. Room.  A record that reaches contention in a group with rank_of[g] >=
+ *     sections[shape_of[g]].cap gets EFULL and contends for nothing.  A caller
+ *     sees the overflow as counts[p] > cap.
+ *  7. Winner.  The lowest arrival index wins a slot, as rule 7 of
+ *     rfec_wire_regroup.  For the winner d, slot_of[d] = rank_of[g] (k_p + n_p)
+ *     + s within the section of p = shape_of[g].  Every other contender gets
+ *     EDUP.  The section's src_of holds the winner's arrival index, or
+ *     RFEC_REGROUP_NONE.
+ *
+ * Written: every element of shape_of [G], rank_of [G], anchor_of [G], counts
+ * [n_plans] and slot_of [n].  In section p, for every row c < cap: present
+ * [c][2], parity_present [c], base_id [c], group_of [c] (the window index g of
+ * the group with rank c) and the row's k_p + n_p entries of src_of; rows with
+ * c >= counts[p] are empty: masks 0, base_id 0, group_of and src_of
+ * RFEC_REGROUP_NONE.  For each filled slot, hdr / meta / fec_size from the
+ * winner's record, as rfec_wire_regroup_index writes them.  Nothing else: the
+ * records of empty slots keep what they held, recs is untouched.  Section p
+ * with groups = min(counts[p], cap) -- or cap, without reading counts back: the
+ * trailing rows decode to nothing -- is then a complete input of
+ * rfec_recover_indexed_out over rfec_wire_parse's payload rows.
+ *
+ * Equivalence: for every g with shape_of[g] == p and rank_of[g] < cap, row
+ * rank_of[g] of section p (hdr, present, meta, fec_size, parity_present,
+ * base_id, src_of) equals row g of what rfec_wire_regroup_index(&plans[p], ...)
+ * writes for the same records, and every record of such a group has the same
+ * slot_of, rebased by (g - rank_of[g]) (k_p + n_p) when it is not negative.
+ *
+ * Checked before any runtime call (RFEC_EINVAL, rfec_last_error names the
+ * argument): each plan (k <= RFEC_MAX_K), n_plans in [1,
+ * RFEC_REGROUP_MAX_SHAPES], no two plans with one (k, row, col), fec_id0 != 0,
+ * groups <= 65535, n <= 0x7FFFFFFF, cap <= groups, NULL pointers (a section
+ * with cap == 0 may hold NULLs; a plan with n_lines == 0 may have NULL meta /
+ * fec_size, its section stays empty; recs and slot_of may be NULL when n == 0)
+ * and alignment: 16 bytes recs; 8 bytes present, parity_present; 4 bytes hdr,
+ * meta, base_id, src_of, group_of, rank_of, anchor_of, counts, slot_of; 2 bytes
+ * fec_size.  groups == 0 touches nothing: every pointer but plans may be NULL.
+ * The buffers must not overlap (not checked).  The call allocates nothing,
+ * copies nothing from the host (plans and sections travel as kernel arguments,
+ * which is what bounds RFEC_REGROUP_MAX_SHAPES), does not synchronise and
+ * launches only on `stream`: six launches (four with n == 0), none waiting on
+ * another workgroup.  slot_of holds intermediate values until the last one has
+ * run.
+ */
+#define RFEC_REGROUP_MAX_SHAPES 32
+#define RFEC_REGROUP_EFULL (-7)
+
+typedef struct {            /* host struct of DEVICE pointers: one shape's section */
+    uint32_t cap;           /* groups the section has room for, 0..groups */
+    uint32_t reserved;
+    rfec_hdr* hdr;              /* [cap][k]      */
+    uint64_t* present;          /* [cap][2]      */
+    rfec_hdr* meta;             /* [cap][n_l]    */
+    uint16_t* fec_size;         /* [cap][n_l]    */
+    uint64_t* parity_present;   /* [cap]         */
+    uint32_t* base_id;          /* [cap]         */
+    uint32_t* src_of;           /* [cap (k+n_l)] */
+    uint32_t* group_of;         /* [cap]: the window index g of the section's row */
+} rfec_regroup_section;
+
+int rfec_wire_regroup_shapes(const rfec_plan* plans, uint32_t n_plans,
+                             const rfec_regroup_section* sections,
+                             uint32_t groups, uint16_t fec_id0,
+                             uint32_t n, const rfec_wire_rec* recs, uint32_t capacity,
+                             uint8_t* shape_of, uint32_t* rank_of, uint32_t* anchor_of,
+                             uint32_t* counts, int32_t* slot_of, void* stream);
 
 /*
  * rfec_recover_batch_out with shards and parity replaced by a row pool and a

@@ -27,14 +27,16 @@ ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 ARCH = os.environ.get("RFEC_OFFLOAD_ARCH", "gfx950")
 
 HIP_SRC = [CSRC / "rfec_kernels.hip", CSRC / "rfec_probe.hip", CSRC / "rfec_wire.hip", CSRC / "rfec_fill.hip",
-           CSRC / "rfec_service.hip", CSRC / "rfec_hostio.hip", CSRC / "rfec_regroup.hip"]
+           CSRC / "rfec_service.hip", CSRC / "rfec_hostio.hip", CSRC / "rfec_regroup.hip",
+           CSRC / "rfec_regroup_shapes.hip"]
 # built once per SIM_VIDEO_SIZE: the C host layer, by concern (rfec_host.c: errors, planner, batched device
 # and wire API; rfec_dropin.c: drop-in symbols + resident service; rfec_hostmem.c: host-memory batches;
 # rfec_sender.c: sender staging; the receiver: rfec_rx_sim.c one shard's arrival-order control plane,
 # rfec_rx_pool.c the replay threads, rfec_rx_plane.c the sharded plane and the host halves of compaction and of
 # the device tables, rfec_rx_dev.c the device side of ingestion, rfec_rx_session.c the sessions), and the flex
 # drop-in; rfec_packed_matrix.c (the packed matrix records' entry points) and rfec_wire_fused.c (the fused encode +
-# SIM_FEC framing's), rfec_wire_regroup.c (parsed datagrams into the batch layout, and its index-only form) and
+# SIM_FEC framing's), rfec_wire_regroup.c (parsed datagrams into the batch layout, its index-only form and the index-only form over
+# a window of several shapes) and
 # rfec_recover_indexed.c (the dense decode through a row map) call launch shims of their own,
 # so they stay out of HOST_SRC: the CPU builds of the host layer compile exactly HOST_SRC against a stub of the runtime
 HOST_NOHIP_SRC = ["rfec_rx_sim.c", "rfec_rx_pool.c", "rfec_rx_plane.c"]  # no GPU runtime: built and tested alone

@@ -157,6 +157,14 @@ int rfec_launch_wire_regroup_index(const rfec_kplan* P, uint32_t groups, uint32_
                                    const rfec_wire_rec* recs, uint32_t capacity, rfec_hdr* hdr, uint64_t* present,
                                    rfec_hdr* meta, uint16_t* fec_size, uint64_t* parity_present, uint32_t* base_id,
                                    uint32_t* src_of, int32_t* slot_of, void* stream);
+/* rfec_wire_regroup_shapes (rfec_wire_regroup.c, kernels in rfec_regroup_shapes.hip): the call's six launches on
+ * `stream` (four with n == 0).  The caller has checked the arguments (n_plans in [1, RFEC_REGROUP_MAX_SHAPES], every
+ * plan with k <= RFEC_MAX_K and its own (k, row, col), groups in [1, 65535], n < 2^31, cap <= groups, the pointers of
+ * the sections with cap > 0); hipErrorInvalidValue otherwise. */
+int rfec_launch_wire_regroup_shapes(const rfec_kplan* plans, uint32_t n_plans, const rfec_regroup_section* sections,
+                                    uint32_t groups, uint32_t fec_id0, uint32_t n, const rfec_wire_rec* recs,
+                                    uint32_t capacity, uint8_t* shape_of, uint32_t* rank_of, uint32_t* anchor_of,
+                                    uint32_t* counts, int32_t* slot_of, void* stream);
 /* rfec_recover_indexed_out (rfec_recover_indexed.c, kernels in rfec_kernels.hip): the dense decode with member and
  * parity rows read from rows [n_rows][stride] through src_of [G (k + n_lines)].  The caller has checked the plan
  * (k <= RFEC_MAX_K), stride a multiple of 16, capacity <= stride, out->per_group in [1, k],

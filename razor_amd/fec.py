@@ -147,6 +147,20 @@ class rfec_plan(C.Structure):
                 f"n_lines={self.n_lines}, lines={self.lines()})")
 
 
+RFEC_REGROUP_MAX_SHAPES = 32
+RFEC_REGROUP_EFULL = -7
+
+
+class rfec_regroup_section(C.Structure):
+    """One shape's section of rfec_wire_regroup_shapes: a host struct of device pointers."""
+    _fields_ = [("cap", C.c_uint32), ("reserved", C.c_uint32), ("hdr", C.c_void_p), ("present", C.c_void_p),
+                ("meta", C.c_void_p), ("fec_size", C.c_void_p), ("parity_present", C.c_void_p),
+                ("base_id", C.c_void_p), ("src_of", C.c_void_p), ("group_of", C.c_void_p)]
+
+
+assert C.sizeof(rfec_regroup_section) == 72
+
+
 class rfec_host_timing(C.Structure):
     _fields_ = [("gather_us", C.c_double), ("h2d_us", C.c_double), ("kernel_us", C.c_double),
                 ("d2h_us", C.c_double), ("scatter_us", C.c_double), ("total_us", C.c_double),
@@ -240,6 +254,8 @@ _SIGS = {
                                     C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rfec_wire_regroup_index": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint16, C.c_uint32, _P, C.c_uint32,
                                           _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rfec_wire_regroup_shapes": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
+                                           C.c_uint32, C.c_uint16, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "rfec_recover_indexed_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32,
                                            _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
@@ -507,6 +523,21 @@ class Native:
         self._check(self.lib.rfec_wire_regroup_index(C.byref(as_plan(plan)), groups, fec_id0, n, recs, capacity, hdr,
                                                      present, meta, fec_size, parity_present, base_id, src_of,
                                                      slot_of, stream), "rfec_wire_regroup_index")
+
+    def wire_regroup_shapes(self, plans, sections, groups, fec_id0, n, recs, capacity, shape_of, rank_of, anchor_of,
+                            counts, slot_of, stream=None):
+        """rfec_wire_regroup_shapes: wire_regroup_index over a window of several shapes in one pass.  plans: a
+        sequence of plans; sections: one rfec_regroup_section (or a dict of its fields) per plan, each then a
+        dense input of recover_indexed_out; shape_of [G] (u8), rank_of, anchor_of [G], counts [len(plans)] (u32)
+        and slot_of [n] (i32) report the classification and the placement."""
+        if len(plans) != len(sections):
+            raise ValueError("one section per plan")
+        pa = (rfec_plan * max(len(plans), 1))(*(as_plan(p) for p in plans))
+        sa = (rfec_regroup_section * max(len(sections), 1))(
+            *(s if isinstance(s, rfec_regroup_section) else rfec_regroup_section(**s) for s in sections))
+        self._check(self.lib.rfec_wire_regroup_shapes(pa, len(plans), sa, groups, fec_id0, n, recs, capacity, shape_of,
+                                                      rank_of, anchor_of, counts, slot_of, stream),
+                    "rfec_wire_regroup_shapes")
 
     def recover_indexed_out(self, plan, groups, stride, capacity, rows, n_rows, src_of, hdr, present, meta, fec_size,
                             parity_present, recovered, per_group, out_shards, out_hdr, out_index, workspace,
