@@ -26,9 +26,11 @@ INCLUDE = ROOT / "include"
 ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 ARCH = os.environ.get("RFEC_OFFLOAD_ARCH", "gfx950")
 
-HIP_SRC = [CSRC / "rfec_kernels.hip", CSRC / "rfec_probe.hip", CSRC / "rfec_wire.hip", CSRC / "rfec_fill.hip",
-           CSRC / "rfec_service.hip", CSRC / "rfec_hostio.hip", CSRC / "rfec_regroup.hip",
-           CSRC / "rfec_regroup_shapes.hip"]
+# rfec_kernels.hip is the dispatch (which kernel family a plan takes, the timing state and the dispatch tag); the
+# families -- encode, peel + replay, fused disjoint decodes, cascade / matrix decodes, the receiver's helpers --
+# are a unit each, reached through the host functions rfec_families.h declares
+HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused", "cascade", "helpers", "probe",
+                                             "wire", "fill", "service", "hostio", "regroup", "regroup_shapes")]
 # built once per SIM_VIDEO_SIZE: the C host layer, by concern (rfec_host.c: errors, planner, batched device
 # and wire API; rfec_dropin.c: drop-in symbols + resident service; rfec_hostmem.c: host-memory batches;
 # rfec_sender.c: sender staging; the receiver: rfec_rx_sim.c one shard's arrival-order control plane,
@@ -47,7 +49,8 @@ C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packe
                                           CSRC / "rfec_recover_indexed.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
-           CSRC / "rfec_host_internal.h"]
+           CSRC / "rfec_host_internal.h", CSRC / "rfec_device.h", CSRC / "rfec_families.h",
+           CSRC / "rfec_regroup_rules.h"]
 # the receiver units' own headers: only the C host layer includes them
 HOST_HEADERS = HEADERS + [CSRC / f"rfec_rx_{u}.h" for u in ("map", "sim", "pool", "plane", "dev")]
 

@@ -9,7 +9,7 @@
  *     (sim_transport/fec/flex_fec_sender.c:81-135, :158-233).
  *  2. The batched device API (rfec_encode_batch / rfec_recover_batch, the
  *     wire codec): argument checks, then the launches through the shims in
- *     rfec_kernels.hip / rfec_wire.hip.
+ *     rfec_kernels.hip (with rfec_fused.hip's for the packed records) / rfec_wire.hip.
  *
  * The rest of the host layer, by concern: rfec_dropin.c (the drop-in
  * flex_fec_generate / flex_fec_recover and the resident service),
@@ -213,8 +213,6 @@ int check_geometry(uint32_t groups, uint32_t stride, uint32_t capacity, uint32_t
 
 /* Pointer alignment (razor_fec.h, "Alignment"): payload slots, the workspace and the packed records move as
  * 16-byte vectors; header records as 32-bit words; masks as 64-bit words; fec_data_size as 16-bit words. */
-static int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 int check_align_in(const uint8_t* shards, const rfec_hdr* hdr, const uint8_t* parity, const rfec_hdr* meta,
                    const uint16_t* fec_size)
 {
@@ -303,13 +301,9 @@ int rfec_recover_batch(const rfec_plan* plan, uint32_t groups, uint32_t stride, 
     if ((rc = check_align_in(shards, hdr, parity, meta, fec_size)) ||
         (rc = check_align_masks(present, parity_present, recovered)))
         return rc;
-    {   /* the fused decode's header lanes: one per (group, line slot), 32-bit lane index */
-        unsigned lg = 1;
-        while ((1u << lg) < plan->n_lines)
-            ++lg;
-        if (((uint64_t)groups << lg) >= (1ull << 32))
-            return set_err(RFEC_EINVAL, "batch too large for one launch (groups x lines)", 0);
-    }
+    /* the fused decode's header lanes: one per (group, line slot), 32-bit lane index */
+    if (((uint64_t)groups << rfec_header_lanes_log2(plan->n_lines)) >= (1ull << 32))
+        return set_err(RFEC_EINVAL, "batch too large for one launch (groups x lines)", 0);
     static __thread rfec_kmask M; /* 1.3 KB: keep it off the stack */
     make_masks(plan, &M);
     const int e = rfec_launch_recover(&M, groups, stride, capacity, shards, hdr, present, parity, meta, fec_size,
@@ -345,13 +339,9 @@ int rfec_recover_batch_out(const rfec_plan* plan, uint32_t groups, uint32_t stri
         return rc;
     static __thread rfec_kmask M;
     make_masks(plan, &M);
-    {   /* header lanes: one per (group, line slot), 32-bit lane index */
-        unsigned lg = 1;
-        while ((1u << lg) < plan->n_lines)
-            ++lg;
-        if (((uint64_t)groups << lg) >= (1ull << 32))
-            return set_err(RFEC_EINVAL, "batch too large for one launch (groups x lines)", 0);
-    }
+    /* header lanes: one per (group, line slot), 32-bit lane index */
+    if (((uint64_t)groups << rfec_header_lanes_log2(plan->n_lines)) >= (1ull << 32))
+        return set_err(RFEC_EINVAL, "batch too large for one launch (groups x lines)", 0);
     const rfec_dense_out D = {out_shards, out_hdr, out_index, per_group};
     const int e = rfec_launch_recover_out(&M, groups, stride, capacity, shards, hdr, present, parity, meta, fec_size,
                                           parity_present, recovered, workspace, stream, g_tuning, &D);
@@ -396,10 +386,7 @@ static int packed_check(const rfec_plan* plan, uint32_t groups, uint32_t per_gro
     if (per_group == 0 || per_group > plan->k)
         return set_err(RFEC_EINVAL, "per_group must be in [1, k]", 0);
     *pk_stride = rfec_packed_stride(plan, per_group);
-    unsigned lg = 0;
-    while ((1u << lg) < per_group)
-        ++lg;
-    if (((uint64_t)groups << lg) >= (1ull << 32) || (uint64_t)groups * *pk_stride >= (1ull << 40))
+    if (((uint64_t)groups << rfec_ceil_log2(per_group)) >= (1ull << 32) || (uint64_t)groups * *pk_stride >= (1ull << 40))
         return set_err(RFEC_EINVAL, "batch too large for one launch (groups x slots)", 0);
     if (groups && (!packed || (uintptr_t)packed % 16))
         return set_err(RFEC_EINVAL, "packed records: NULL or not 16-byte aligned", 0);

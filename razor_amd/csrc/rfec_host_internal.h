@@ -20,6 +20,9 @@
 
 #pragma GCC visibility push(hidden)
 
+/* p is not a multiple of a (a power of two); NULL passes */
+static inline int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
 /* rfec_host.c: the thread's last error (rfec_last_error), with the HIP error
  * string when hip_code != 0; returns code */
 int set_err(int code, const char* what, int hip_code);

@@ -27,32 +27,9 @@
 // nothing else of the line where flex_fec_generate fails; the recovered-segment
 // scatter writes what flex_fec_recover writes (flex_fec_xor.c:64-101) plus the
 // group's fec_id, the whole data array.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "rfec_internal.h"
-#include "rfec_launch.h"
+#include "rfec_device.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-struct FastDiv {
-    uint32_t d, m, s;
-};
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f)
-{
-    return (uint32_t)(((uint64_t)__umulhi(n, f.m) + n) >> f.s);
-}
-FastDiv make_fastdiv(uint32_t d)
-{
-    uint32_t s = 0;
-    while ((1ull << s) < d)
-        ++s;
-    const uint64_t m = ((1ull << 32) * ((1ull << s) - d)) / d + 1;
-    return FastDiv{d, (uint32_t)m, s};
-}
 
 // lane i + 1's value (0 in lane 63): DPP wave_shl:1; every lane must take part
 __device__ __forceinline__ uint32_t next_lane(uint32_t v)
@@ -306,8 +283,6 @@ __global__ __launch_bounds__(kBlock) void k_host_scatter_seg(const uint64_t* __r
     const uint64_t pm = ppm[g];
     st_host2(p + 20, pm ? fecid[(size_t)g * n + (uint32_t)__ffsll((long long)pm) - 1u] : 0u); // the group's fec_id
 }
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
 
 // Sender staging without a host copy (rfec_sender.c rfec_host_send_frames,
 // frames in rfec_pinned_alloc memory): slot s <- the segment bytes [src[s],

@@ -1,5 +1,6 @@
 /* rfec_internal.h -- contract between the C host layer (rfec_host.c) and the
- * HIP launch shim (rfec_kernels.hip).  Not installed. */
+ * HIP launch shims (rfec_kernels.hip: the batched encode / recover dispatch; the other .hip units: their own).
+ * Not installed. */
 #ifndef RFEC_INTERNAL_H_
 #define RFEC_INTERNAL_H_
 
@@ -16,6 +17,17 @@ typedef struct {
     rfec_kplan plan;
     uint64_t mask[RFEC_MAX_LINES][2];
 } rfec_kmask;
+
+/* the least lg with 2^lg >= x (0 for x <= 1): lanes per group of the header and pack kernels */
+static inline uint32_t rfec_ceil_log2(uint32_t x)
+{
+    uint32_t lg = 0;
+    while ((1ull << lg) < x)
+        ++lg;
+    return lg;
+}
+/* the fused decodes' header lanes per group: a power of two >= n_lines, at least 2 */
+static inline uint32_t rfec_header_lanes_log2(uint32_t n_lines) { return n_lines > 2 ? rfec_ceil_log2(n_lines) : 1u; }
 
 /* kernel flags == the RFEC_TUNE_* bits of razor_fec.h */
 #define RFEC_KFLAG_GENERIC RFEC_TUNE_GENERIC
@@ -165,7 +177,7 @@ int rfec_launch_wire_regroup_shapes(const rfec_kplan* plans, uint32_t n_plans, c
                                     uint32_t groups, uint32_t fec_id0, uint32_t n, const rfec_wire_rec* recs,
                                     uint32_t capacity, uint8_t* shape_of, uint32_t* rank_of, uint32_t* anchor_of,
                                     uint32_t* counts, int32_t* slot_of, void* stream);
-/* rfec_recover_indexed_out (rfec_recover_indexed.c, kernels in rfec_kernels.hip): the dense decode with member and
+/* rfec_recover_indexed_out (rfec_recover_indexed.c, kernels in rfec_fused.hip / rfec_peel.hip): the dense decode with member and
  * parity rows read from rows [n_rows][stride] through src_of [G (k + n_lines)].  The caller has checked the plan
  * (k <= RFEC_MAX_K), stride a multiple of 16, capacity <= stride, out->per_group in [1, k],
  * groups * per_group * CD < 2^31, groups << ceil(log2 n_lines) < 2^32 and the pointers; hipErrorInvalidValue

@@ -2,7 +2,7 @@
  * rfec_packed_matrix.c -- packed erasure records for the sender's full row +
  * column plans of k = 6..16 (razor_fec.h: rfec_packed_matrix_stride,
  * rfec_pack_erasures_matrix, rfec_recover_packed_matrix_out): argument
- * checks, then the launches through the shims in rfec_kernels.hip.  The
+ * checks, then the launches through the shims in rfec_cascade.hip.  The
  * row-layout records' entry points (rfec_host.c) keep refusing these plans.
  *
  * Not one of build.py's HOST_SRC: the CPU builds of the host layer link
@@ -41,11 +41,8 @@ static int matrix_check(const rfec_plan* plan, uint32_t groups, uint32_t per_gro
     if (per_group == 0 || per_group > plan->k)
         return set_err(RFEC_EINVAL, "per_group must be in [1, k]", 0);
     *pk_stride = rfec_packed_matrix_stride(plan, per_group);
-    unsigned lg = 0;
-    while ((1u << lg) < per_group)
-        ++lg;
     /* (the pack kernel's lanes: one per 16 bytes of the records) */
-    if (((uint64_t)groups << lg) >= (1ull << 32) || (uint64_t)groups * *pk_stride >= (1ull << 40) ||
+    if (((uint64_t)groups << rfec_ceil_log2(per_group)) >= (1ull << 32) || (uint64_t)groups * *pk_stride >= (1ull << 40) ||
         (uint64_t)groups * (*pk_stride / 16) >= (1ull << 32))
         return set_err(RFEC_EINVAL, "batch too large for one launch (groups x slots)", 0);
     if (groups && (!packed || (uintptr_t)packed % 16))

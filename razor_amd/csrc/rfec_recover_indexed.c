@@ -13,8 +13,6 @@
 #include "rfec_internal.h"
 #include "rfec_host_internal.h"
 
-static int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 int rfec_recover_indexed_out(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
                              const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of, const rfec_hdr* hdr,
                              const uint64_t* present, const rfec_hdr* meta, const uint16_t* fec_size,
@@ -47,13 +45,9 @@ int rfec_recover_indexed_out(const rfec_plan* plan, uint32_t groups, uint32_t st
         return set_err(RFEC_EINVAL, "src_of, hdr, meta and out_hdr must be 4-byte aligned", 0);
     if (misaligned(fec_size, 2))
         return set_err(RFEC_EINVAL, "fec_size must be 2-byte aligned", 0);
-    {   /* header lanes: one per (group, line slot), 32-bit lane index */
-        unsigned lg = 1;
-        while ((1u << lg) < plan->n_lines)
-            ++lg;
-        if (((uint64_t)groups << lg) >= (1ull << 32))
-            return set_err(RFEC_EINVAL, "batch too large for one launch (groups x lines)", 0);
-    }
+    /* header lanes: one per (group, line slot), 32-bit lane index */
+    if (((uint64_t)groups << rfec_header_lanes_log2(plan->n_lines)) >= (1ull << 32))
+        return set_err(RFEC_EINVAL, "batch too large for one launch (groups x lines)", 0);
     static __thread rfec_kmask M; /* 1.3 KB: keep it off the stack */
     make_masks(plan, &M);
     const rfec_dense_out D = {out_shards, out_hdr, out_index, per_group};

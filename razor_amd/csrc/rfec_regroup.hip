@@ -28,65 +28,9 @@
 // of rfec_recover_indexed_out.
 // The rows are loaded non-temporally (each is read once) and stored with the default policy: the decode reads
 // them next.  Row and record addresses are 64-bit (records x stride passes 4 GiB on the large shapes).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "rfec_internal.h"
-#include "rfec_launch.h"
+#include "rfec_regroup_rules.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr uint32_t kNone = RFEC_REGROUP_NONE;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-// CUTLASS-style fast unsigned division for dividends < 2^31.
-struct FastDiv {
-    uint32_t d, m, s;
-};
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f)
-{
-    return (uint32_t)(((uint64_t)__umulhi(n, f.m) + n) >> f.s);
-}
-FastDiv make_fastdiv(uint32_t d)
-{
-    uint32_t s = 0;
-    while ((1ull << s) < d)
-        ++s;
-    const uint64_t m = ((1ull << 32) * ((1ull << s) - d)) / d + 1;
-    return FastDiv{d, (uint32_t)m, s};
-}
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
-// payload rows: read once
-__device__ __forceinline__ v4u ld16(const v4u* p) { return __builtin_nontemporal_load(p); }
-
-static_assert(sizeof(rfec_wire_rec) == 64 && sizeof(rfec_hdr) == 20, "record layouts");
-// rfec_wire_rec as sixteen 32-bit words (razor_fec.h): 0 status | ver | mid | remb, 2-6 hdr (2 = seq), 7 base_id,
-// 9 fec_id | count, 10 transport_seq | data_size, 11 row | col | index
-struct Rec {
-    uint32_t tag, seq, base_id, fec_id, count, data_size, shape; // shape: row | col << 8 | index << 16
-};
-__device__ __forceinline__ Rec load_rec(const rfec_wire_rec* __restrict__ recs, uint32_t r)
-{
-    const v4u* p = reinterpret_cast<const v4u*>(recs + r); // 16-byte aligned (checked by the entry point)
-    const v4u a = p[0], b = p[1], c = p[2];
-    Rec R;
-    R.tag = a.x;
-    R.seq = a.z;
-    R.base_id = b.w;
-    R.fec_id = c.y & 0xFFFFu;
-    R.count = c.y >> 16;
-    R.data_size = c.z >> 16;
-    R.shape = c.w & 0xFFFFFFu;
-    return R;
-}
-
-// the base_id of record a (an anchor)
-__device__ __forceinline__ uint32_t base_id_of(const rfec_wire_rec* __restrict__ recs, uint32_t a)
-{
-    return reinterpret_cast<const uint32_t*>(recs + a)[7];
-}
 
 struct RgArgs {
     const rfec_wire_rec* recs;
@@ -99,20 +43,7 @@ struct RgArgs {
     uint8_t index[RFEC_MAX_LINES]; // plan->line[l].index
 };
 
-// rule 1: 0 = ENOTFEC, else the mid (status == RFEC_WIRE_OK and SIM_SEG or SIM_FEC)
-__device__ __forceinline__ uint32_t kind_of(uint32_t tag)
-{
-    const uint32_t mid = (tag >> 16) & 0xFFu;
-    return (tag & 0xFFu) == RFEC_WIRE_OK && (mid == RFEC_WIRE_SEG || mid == RFEC_WIRE_FEC) ? mid : 0u;
-}
-// rule 2: the group index, or kNone (EWINDOW)
-__device__ __forceinline__ uint32_t group_of(uint32_t fec_id, const RgArgs& A)
-{
-    if (fec_id == 0)
-        return kNone;
-    const uint32_t g = fec_id >= A.fec_id0 ? fec_id - A.fec_id0 : fec_id + 65535u - A.fec_id0;
-    return g < A.groups ? g : kNone;
-}
+// (rule 1: kind_of; rule 2: group_of -- rfec_regroup_rules.h)
 // rule 3: the line of a shape-accepted SIM_FEC, or kNone (ESHAPE)
 __device__ __forceinline__ uint32_t line_of(const Rec& R, const RgArgs& A)
 {
@@ -143,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void k_regroup_anchor(const RgArgs A)
     const Rec R = load_rec(A.recs, r);
     if (kind_of(R.tag) != RFEC_WIRE_FEC)
         return;
-    const uint32_t g = group_of(R.fec_id, A);
+    const uint32_t g = group_of(R.fec_id, A.fec_id0, A.groups);
     if (g == kNone || line_of(R, A) == kNone)
         return;
     atomicMin(A.anchor + g, r);
@@ -160,7 +91,7 @@ __global__ __launch_bounds__(kBlock) void k_regroup_contend(const RgArgs A)
     uint32_t g = kNone, s = kNone;
     if (!kind)
         res = RFEC_REGROUP_ENOTFEC;
-    else if ((g = group_of(R.fec_id, A)) == kNone)
+    else if ((g = group_of(R.fec_id, A.fec_id0, A.groups)) == kNone)
         res = RFEC_REGROUP_EWINDOW;
     else if (kind == RFEC_WIRE_FEC) {
         const uint32_t l = line_of(R, A);
@@ -229,30 +160,15 @@ __global__ __launch_bounds__(kBlock) void k_regroup_place(const RgArgs A, const 
         const uint32_t* w = reinterpret_cast<const uint32_t*>(A.recs + a);
         const bool seg = s < A.k;
         const size_t o = seg ? (size_t)g * A.k + s : (size_t)g * A.n_lines + (s - A.k);
-        uint32_t* h = reinterpret_cast<uint32_t*>((seg ? P.hdr : P.meta) + o);
-#pragma unroll
-        for (int q = 0; q < 5; ++q)
-            h[q] = w[2 + q];
-        if (!seg)
-            P.fec_size[o] = (uint16_t)(w[10] >> 16);
+        place_record(w, reinterpret_cast<uint32_t*>((seg ? P.hdr : P.meta) + o), !seg, P.fec_size + o);
         return;
     }
     t -= P.n_slots;
     if (t < A.groups) { // group: the masks, and the anchor's base_id in place of its arrival index
-        const uint32_t* so = A.src_of + (size_t)t * A.slots;
-        uint64_t m0 = 0, m1 = 0, pp = 0;
-        for (uint32_t i = 0; i < A.k; ++i) {
-            const uint64_t bit = so[i] != kNone;
-            if (i < 64)
-                m0 |= bit << i;
-            else
-                m1 |= bit << (i - 64);
-        }
-        for (uint32_t l = 0; l < A.n_lines; ++l)
-            pp |= (uint64_t)(so[A.k + l] != kNone) << l;
-        P.present[2 * (size_t)t] = m0;
-        P.present[2 * (size_t)t + 1] = m1;
-        P.parity_present[t] = pp;
+        const SlotMasks m = slot_masks(A.src_of + (size_t)t * A.slots, A.k, A.n_lines);
+        P.present[2 * (size_t)t] = m.present[0];
+        P.present[2 * (size_t)t + 1] = m.present[1];
+        P.parity_present[t] = m.parity_present;
         const uint32_t a = A.anchor[t];
         A.anchor[t] = a == kNone ? 0u : base_id_of(A.recs, a);
         return;

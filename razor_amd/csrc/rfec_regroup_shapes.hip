@@ -28,16 +28,10 @@
 // so that they come through scalar loads and not through a gather from the argument block.
 // The plans' keys and line indices and the sections' pointers travel as kernel arguments (at most 2,888 bytes of the
 // 4,096 an argument block holds, with RFEC_REGROUP_MAX_SHAPES = 32).  Record addresses are 64-bit.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "rfec_internal.h"
-#include "rfec_launch.h"
+#include "rfec_regroup_rules.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr uint32_t kNone = RFEC_REGROUP_NONE;
 constexpr uint32_t kShapes = RFEC_REGROUP_MAX_SHAPES;
 constexpr uint32_t kNoShape = 0xFFu;
 // between k_shapes_contend and k_shapes_tables a contender's slot_of holds slot | plan << kSlotBits
@@ -48,35 +42,8 @@ static_assert(65535u * (RFEC_MAX_K + RFEC_MAX_LINES) < (1u << kSlotBits) && kSha
 constexpr int kRankBlock = 512;
 constexpr int kRankChunk = 16;
 constexpr uint32_t kRankTile = kRankBlock * kRankChunk;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
-static_assert(sizeof(rfec_wire_rec) == 64 && sizeof(rfec_hdr) == 20, "record layouts");
 static_assert(kShapes * 16 == kRankBlock, "k_shapes_rank scans a shape's counters with 16 lanes");
-// rfec_wire_rec as sixteen 32-bit words (razor_fec.h): 0 status | ver | mid | remb, 2-6 hdr (2 = seq), 7 base_id,
-// 9 fec_id | count, 10 transport_seq | data_size, 11 row | col | index
-struct Rec {
-    uint32_t tag, seq, base_id, fec_id, count, data_size, shape; // shape: row | col << 8 | index << 16
-};
-__device__ __forceinline__ Rec load_rec(const rfec_wire_rec* __restrict__ recs, uint32_t r)
-{
-    const v4u* p = reinterpret_cast<const v4u*>(recs + r); // 16-byte aligned (checked by the entry point)
-    const v4u a = p[0], b = p[1], c = p[2];
-    Rec R;
-    R.tag = a.x;
-    R.seq = a.z;
-    R.base_id = b.w;
-    R.fec_id = c.y & 0xFFFFu;
-    R.count = c.y >> 16;
-    R.data_size = c.z >> 16;
-    R.shape = c.w & 0xFFFFFFu;
-    return R;
-}
-__device__ __forceinline__ uint32_t word_of(const rfec_wire_rec* __restrict__ recs, uint32_t r, int w)
-{
-    return reinterpret_cast<const uint32_t*>(recs + r)[w];
-}
 
 // the window and the plans' keys
 struct Win {
@@ -125,20 +92,7 @@ __device__ __forceinline__ uint32_t section_of(const uint32_t* off, uint32_t n_p
     return p;
 }
 
-// rule 1: 0 = ENOTFEC, else the mid (status == RFEC_WIRE_OK and SIM_SEG or SIM_FEC)
-__device__ __forceinline__ uint32_t kind_of(uint32_t tag)
-{
-    const uint32_t mid = (tag >> 16) & 0xFFu;
-    return (tag & 0xFFu) == RFEC_WIRE_OK && (mid == RFEC_WIRE_SEG || mid == RFEC_WIRE_FEC) ? mid : 0u;
-}
-// rule 1: the group index, or kNone (EWINDOW)
-__device__ __forceinline__ uint32_t group_of(uint32_t fec_id, const Win& W)
-{
-    if (fec_id == 0)
-        return kNone;
-    const uint32_t g = fec_id >= W.fec_id0 ? fec_id - W.fec_id0 : fec_id + 65535u - W.fec_id0;
-    return g < W.groups ? g : kNone;
-}
+// (rule 1: kind_of and group_of -- rfec_regroup_rules.h)
 // the plan with a SIM_FEC's (count, row, col), or kNoShape: the plans differ pairwise in them
 __device__ __forceinline__ uint32_t plan_of(uint32_t count, uint32_t rowcol, const Win& W)
 {
@@ -211,7 +165,7 @@ __global__ __launch_bounds__(kBlock) void k_shapes_anchor(const Win W, const Lin
     const Rec R = load_rec(W.recs, r);
     if (kind_of(R.tag) != RFEC_WIRE_FEC)
         return;
-    const uint32_t g = group_of(R.fec_id, W);
+    const uint32_t g = group_of(R.fec_id, W.fec_id0, W.groups);
     uint32_t l;
     if (g == kNone || accept(R, W, L, l) == kNoShape)
         return;
@@ -325,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void k_shapes_contend(const Win W, const Li
     uint32_t g = kNone, s = kNone, p = kNoShape; // s: a segment's member index, a parity's line
     if (!kind)
         res = RFEC_REGROUP_ENOTFEC;
-    else if ((g = group_of(R.fec_id, W)) == kNone)
+    else if ((g = group_of(R.fec_id, W.fec_id0, W.groups)) == kNone)
         res = RFEC_REGROUP_EWINDOW;
     else if (kind == RFEC_WIRE_FEC) {
         const uint32_t mine = accept(R, W, L, s);
@@ -334,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void k_shapes_contend(const Win W, const Li
             res = RFEC_REGROUP_ESHAPE;
         else {
             const uint32_t a = U.anchor_of[g];
-            const uint32_t base = a == r ? R.base_id : word_of(W.recs, a, 7);
+            const uint32_t base = a == r ? R.base_id : base_id_of(W.recs, a);
             res = R.base_id == base ? 0 : RFEC_REGROUP_EBASE;
         }
     } else {
@@ -342,7 +296,7 @@ __global__ __launch_bounds__(kBlock) void k_shapes_contend(const Win W, const Li
         if (a == kNone || (p = U.shape_of[g]) == kNoShape) // (an anchor always has a shape)
             res = RFEC_REGROUP_ENOPARITY;
         else {
-            s = R.seq - word_of(W.recs, a, 7); // unsigned: a packet id below the base is far above k
+            s = R.seq - base_id_of(W.recs, a); // unsigned: a packet id below the base is far above k
             res = 0;
         }
     }
@@ -383,12 +337,7 @@ __global__ __launch_bounds__(kBlock) void k_shapes_tables(const Win W, const Out
             const uint32_t* w = reinterpret_cast<const uint32_t*>(W.recs + a);
             const bool seg = s < k;
             const size_t o = seg ? (size_t)c * k + s : (size_t)c * nl + (s - k);
-            uint32_t* h = reinterpret_cast<uint32_t*>((seg ? T.hdr[p] : T.meta[p]) + o);
-#pragma unroll
-            for (int q = 0; q < 5; ++q)
-                h[q] = w[2 + q];
-            if (!seg)
-                T.fec_size[p][o] = (uint16_t)(w[10] >> 16);
+            place_record(w, reinterpret_cast<uint32_t*>((seg ? T.hdr[p] : T.meta[p]) + o), !seg, T.fec_size[p] + o);
         });
         return;
     }
@@ -396,22 +345,12 @@ __global__ __launch_bounds__(kBlock) void k_shapes_tables(const Win W, const Out
     if (t < n_rows) { // section row: the masks and the anchor's base_id (an empty row: 0)
         for_plan(section_of(O.row0, W.n_plans, t), [&](uint32_t p) {
             const uint32_t c = t - O.row0[p], k = W.k[p], nl = W.nl[p];
-            const uint32_t* so = M.src_of[p] + (size_t)c * (k + nl);
-            uint64_t m0 = 0, m1 = 0, pp = 0;
-            for (uint32_t i = 0; i < k; ++i) {
-                const uint64_t bit = so[i] != kNone;
-                if (i < 64)
-                    m0 |= bit << i;
-                else
-                    m1 |= bit << (i - 64);
-            }
-            for (uint32_t l = 0; l < nl; ++l)
-                pp |= (uint64_t)(so[k + l] != kNone) << l;
-            T.present[p][2 * (size_t)c] = m0;
-            T.present[p][2 * (size_t)c + 1] = m1;
-            T.parity_present[p][c] = pp;
+            const SlotMasks m = slot_masks(M.src_of[p] + (size_t)c * (k + nl), k, nl);
+            T.present[p][2 * (size_t)c] = m.present[0];
+            T.present[p][2 * (size_t)c + 1] = m.present[1];
+            T.parity_present[p][c] = m.parity_present;
             const uint32_t g = M.group_of[p][c];
-            T.base_id[p][c] = g == kNone ? 0u : word_of(W.recs, U.anchor_of[g], 7);
+            T.base_id[p][c] = g == kNone ? 0u : base_id_of(W.recs, U.anchor_of[g]);
         });
         return;
     }

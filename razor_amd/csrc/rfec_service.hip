@@ -6,7 +6,7 @@
 // service").
 //
 // Arithmetic restated from the reference (yuanrongxi/razor), as the batch
-// kernels of rfec_kernels.hip:
+// kernels of rfec_encode.hip and the decode units:
 //   parity payload  = XOR of zero-padded member payloads  flex_fec_xor.c:30-32, 46-49
 //   parity meta     = XOR of member headers, max data_size flex_fec_xor.c:13-26, 37-44
 //   recovery        = parity ^ XOR of present members, refused when a member is

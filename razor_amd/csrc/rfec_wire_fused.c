@@ -19,8 +19,6 @@
 #define WEF_MAX_DSTRIDE 1280u        /* the quarter-wave window */
 #define WEF_OFFSETS 0xFFFFFFF0ull    /* buffer offsets stay below this */
 
-static int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-
 /* The most groups one launch takes: (groups k + 4) stride + 1280 (the bound the quarter-wave framing states for
  * its input slots), the header records' groups k 20 bytes and, when the launch's output is its own slice of
  * dgram (own_out), groups n dstride, all below WEF_OFFSETS.  At least 1: a group is at most 255 slots of 2 KiB. */

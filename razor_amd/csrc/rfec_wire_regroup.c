@@ -15,7 +15,16 @@
 #include "rfec_internal.h"
 #include "rfec_host_internal.h"
 
-static int misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+static int check_window(uint16_t fec_id0, uint32_t groups, uint32_t n)
+{
+    if (fec_id0 == 0)
+        return set_err(RFEC_EINVAL, "fec_id0 must not be 0 (the sender skips it)", 0);
+    if (groups > 65535u)
+        return set_err(RFEC_EINVAL, "groups must be <= 65535 (the fec_ids of one succession)", 0);
+    if (n > 0x7FFFFFFFu)
+        return set_err(RFEC_EINVAL, "n must be <= 0x7FFFFFFF", 0);
+    return RFEC_OK;
+}
 
 int rfec_wire_regroup(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0, uint32_t n,
                       const rfec_wire_rec* recs, const uint8_t* payload, uint32_t stride, uint32_t capacity,
@@ -31,12 +40,8 @@ int rfec_wire_regroup(const rfec_plan* plan, uint32_t groups, uint16_t fec_id0, 
         return set_err(RFEC_EINVAL, "stride must be a positive multiple of 16, at most 2048", 0);
     if (capacity > stride)
         return set_err(RFEC_EINVAL, "capacity must be <= stride", 0);
-    if (fec_id0 == 0)
-        return set_err(RFEC_EINVAL, "fec_id0 must not be 0 (the sender skips it)", 0);
-    if (groups > 65535u)
-        return set_err(RFEC_EINVAL, "groups must be <= 65535 (the fec_ids of one succession)", 0);
-    if (n > 0x7FFFFFFFu)
-        return set_err(RFEC_EINVAL, "n must be <= 0x7FFFFFFF", 0);
+    if ((rc = check_window(fec_id0, groups, n)) != RFEC_OK)
+        return rc;
     if (groups == 0)
         return RFEC_OK;
     const int nl = plan->n_lines;
@@ -70,12 +75,8 @@ int rfec_wire_regroup_index(const rfec_plan* plan, uint32_t groups, uint16_t fec
     int rc = check_plan(plan, RFEC_MAX_K);
     if (rc)
         return rc;
-    if (fec_id0 == 0)
-        return set_err(RFEC_EINVAL, "fec_id0 must not be 0 (the sender skips it)", 0);
-    if (groups > 65535u)
-        return set_err(RFEC_EINVAL, "groups must be <= 65535 (the fec_ids of one succession)", 0);
-    if (n > 0x7FFFFFFFu)
-        return set_err(RFEC_EINVAL, "n must be <= 0x7FFFFFFF", 0);
+    if ((rc = check_window(fec_id0, groups, n)) != RFEC_OK)
+        return rc;
     if (groups == 0)
         return RFEC_OK;
     const int nl = plan->n_lines;
@@ -126,12 +127,9 @@ int rfec_wire_regroup_shapes(const rfec_plan* plans, uint32_t n_plans, const rfe
             if (plans[q].k == plans[p].k && plans[q].row == plans[p].row && plans[q].col == plans[p].col)
                 return shapes_err("plans", p, " repeats the (k, row, col) of an earlier plan");
     }
-    if (fec_id0 == 0)
-        return set_err(RFEC_EINVAL, "fec_id0 must not be 0 (the sender skips it)", 0);
-    if (groups > 65535u)
-        return set_err(RFEC_EINVAL, "groups must be <= 65535 (the fec_ids of one succession)", 0);
-    if (n > 0x7FFFFFFFu)
-        return set_err(RFEC_EINVAL, "n must be <= 0x7FFFFFFF", 0);
+    const int rc = check_window(fec_id0, groups, n);
+    if (rc)
+        return rc;
     for (uint32_t p = 0; sections && p < n_plans; ++p)
         if (sections[p].cap > groups)
             return shapes_err("sections", p, ".cap must be <= groups");

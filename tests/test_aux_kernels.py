@@ -1,5 +1,5 @@
 """The helper kernels around the codec, on their own (aux_kernel_cases.py):
-k_rx_split, k_gather_rows, k_rx_stage, k_line_jobs (rfec_kernels.hip),
+k_rx_split, k_gather_rows, k_rx_stage, k_line_jobs (rfec_helpers.hip),
 k_send_gather (rfec_hostio.hip) and the split entries the parse writes beside
 its records (k_parse_q's split_entry + the CRC rewrite, or k_rx_split after a
 wave parse; rfec_wire.hip), bit-exact against numpy restatements.

@@ -192,7 +192,7 @@ def test_arena_layout_is_minimally_aligned():
 # ---------------------------------------------------------------------------------------------------------------
 # the decodes on both sides of the buffer-descriptor bound
 # ---------------------------------------------------------------------------------------------------------------
-K_WAVE, K_NOLOAD = 64, 0x7FFFFFF0  # rfec_kernels.hip kWave, kNoLoad
+K_WAVE, K_NOLOAD = 64, 0x7FFFFFF0  # rfec_device.h kWave, kNoLoad
 BOUND_K, BOUND_G, BOUND_CAP = 10, 66, 16
 
 
