@@ -138,6 +138,38 @@ class GpuEngine(ga.ArenaEngine):
                 A.get("out_index", np.uint8, (G, E)), A.get("recovered", np.uint64, (G, 2)),
                 A.get("packed", np.uint8, (G, pks)))
 
+    def recover_packed_matrix(self, plan, shards, hdr, present, parity, meta, fsize, pp, capacity, per_group):
+        """rfec_pack_erasures_matrix on the device then rfec_recover_packed_matrix_out, every buffer in one
+        guarded arena: returns (out_shards, out_hdr, out_index, recovered, packed records [G][stride])."""
+        G, k, stride = shards.shape
+        E = per_group
+        n = plan.n_lines
+        pks = self.lib.packed_matrix_stride(plan, E)
+        assert pks > 0 and pks % 64 == 0
+        B = ga.Buf
+        A = ga.Arena(self.be, [
+            B("shards", shards.size, shards, "in"), B("parity", G * n * stride, parity, "in"),
+            B("hdr", G * k * ga.HDR_BYTES, hdr, "in"),
+            B("present", G * 16, np.ascontiguousarray(present, np.uint64), "in"),
+            B("meta", G * n * ga.HDR_BYTES, meta, "in"),
+            B("fec_size", G * n * 2, np.ascontiguousarray(fsize, np.uint16), "in"),
+            B("parity_present", G * 8, np.ascontiguousarray(pp, np.uint64), "in"),
+            B("packed", G * pks, 0x77, "out"), B("recovered", G * 16, 0xEE, "out"),
+            B("out_shards", G * E * stride, 0x3C, "out"), B("out_hdr", G * E * ga.HDR_BYTES, 0x3C, "out"),
+            B("out_index", G * E, 0x3C, "out")])
+        st = self._stream()
+        self.lib.pack_erasures_matrix(plan, G, *(A.ptr(n) for n in ("hdr", "present", "meta", "fec_size",
+                                                                    "parity_present")), E, A.ptr("packed"), st)
+        self.pack_path = int(self.lib.lib.rfec_last_path())
+        self.lib.recover_packed_matrix_out(plan, G, stride, capacity, A.ptr("shards"), A.ptr("parity"),
+                                           A.ptr("packed"), A.ptr("recovered"), E, A.ptr("out_shards"),
+                                           A.ptr("out_hdr"), A.ptr("out_index"), st)
+        self.last_path = int(self.lib.lib.rfec_last_path())
+        self._finish(A, "recover_packed_matrix")
+        return (A.get("out_shards", np.uint8, (G, E, stride)), A.get("out_hdr", HDR_DTYPE, (G, E)),
+                A.get("out_index", np.uint8, (G, E)), A.get("recovered", np.uint64, (G, 2)),
+                A.get("packed", np.uint8, (G, pks)))
+
 
 class GpuWire:
     """The wire codec (rfec_wire_*) on numpy inputs."""
