@@ -1,6 +1,7 @@
 // rfec_cascade.hip -- the cascade and matrix decodes of the flex-FEC engine (gfx950), the packed matrix
-// records' packer and decode, and their launchers; rfec_kernels.hip picks the cascade decode
-// (rfec_launch_recover[_out]), rfec_packed_matrix.c calls the packed records' shims.
+// records' packer and decode, the matrix decode through a slot map over a row pool, and their launchers;
+// rfec_kernels.hip picks the cascade decode (rfec_launch_recover[_out]), rfec_packed_matrix.c calls the packed
+// records' shims, rfec_recover_indexed_matrix.c the indexed matrix decode's.
 #include "rfec_families.h"
 
 namespace {
@@ -780,6 +781,155 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         matrix_payload_block<K, COL>(A, HS, pb);
 }
 
+// The same decode through a slot map over a row pool (rfec_recover_indexed_matrix_out): the checker half is
+// k_decode_matrix_dense's unchanged -- it reads the tables only -- and a payload lane reads member i of its group
+// from row so[i] of the pool and parity line l from row so[K + l] (so: the group's K + NL words of src_of; pool:
+// chunk j of row 0).  The rows lie anywhere in the pool, so no descriptor spans a wave's loads (wave_rsrc / bld16 do
+// not carry over): they are plain 64-bit addresses, as in k_decode_rows_indexed -- the map words of the wanted
+// slots first, then the parity and the MX member chunks unconditionally and in flight together; a member that is
+// not wanted (past the line's end, or the target) re-reads the parity chunk and is XORed as zero.  A row index is
+// clamped to `last` = n_rows - 1 before it is used (pool_row).  Only the entries of present members and received
+// parities are read: a line fires, or takes a step of the schedule, with its parity received, and a member that
+// was not received comes from the dense out slot where an earlier step stored it.
+//
+// The replay is a copy of cascade_replay, not a row-source parameter of it: the existing kernels' code stays as
+// it is.
+template <class Lines>
+__device__ __forceinline__ v4u cascade_replay_indexed(const CSched& S, uint32_t need, uint32_t ss, uint64_t erased,
+                                                      const v4u* pool, const uint32_t* __restrict__ so, uint32_t K,
+                                                      uint32_t last, v4u* slot0, uint32_t E, uint32_t C,
+                                                      const Lines& LL)
+{
+    v4u res = {0, 0, 0, 0};
+#pragma unroll 1
+    for (uint32_t s = 0; s < 8; ++s) {
+        if (!((need >> s) & 1u))
+            continue;
+        const uint32_t l = cs_line(S, s), t = cs_tg(S, s), ln = LL.rec(l);
+        const uint32_t first = ln & 0xff, stride = (ln >> 8) & 0xff, count = (ln >> 16) & 0xff;
+        v4u acc = ld16(pool_row(pool, so, K + l, last, C));
+        v4u mv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t i = first + u * stride;
+            mv[u] = v4u{0, 0, 0, 0};
+            if ((uint32_t)u < count && i != t)
+                mv[u] = ld16(((erased >> i) & 1ull) ? slot0 + (size_t)cs_slot(E, erased, i) * C
+                                                    : pool_row(pool, so, i, last, C));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            acc ^= mv[u];
+        if (s == ss) {
+            res = acc;
+            break;
+        }
+        st16(slot0 + (size_t)cs_slot(E, erased, t) * C, acc);
+    }
+    return res;
+}
+
+// cascade_dense_tail over the pool (MatLines serve both the schedule and the replay)
+template <class Lines>
+__device__ __forceinline__ void cascade_dense_tail_indexed(const CascArgs& A, const Lines& LL, uint32_t NL, uint32_t have,
+                                                           uint32_t erased, uint32_t ppm, uint32_t tgt, const v4u* pool,
+                                                           const uint32_t* __restrict__ so, uint32_t K, uint32_t last,
+                                                           v4u* slot0, v4u* dst)
+{
+    const CSched S = cascade_schedule<uint32_t>(LL, NL, have, ppm, 0u, erased, A.E);
+    uint32_t ss = 8;
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+        if ((uint32_t)s < S.n && cs_tg(S, s) == tgt)
+            ss = s;
+    if (ss == 8)
+        return; // not recoverable
+    uint32_t need = 1u << ss;
+#pragma unroll 1
+    for (int s = (int)ss; s >= 0; --s) {
+        if (!((need >> s) & 1u))
+            continue;
+        const uint64_t dm = LL.mask(cs_line(S, s)) & erased & ~(1ull << cs_tg(S, s));
+        for (int s2 = 0; s2 < s; ++s2)
+            if ((dm >> cs_tg(S, s2)) & 1ull)
+                need |= 1u << s2;
+    }
+    st16(dst, cascade_replay_indexed(S, need, ss, erased, pool, so, K, last, slot0, A.E, A.C, LL));
+}
+
+template <int K, int COL>
+__device__ __forceinline__ void matrix_payload_block_indexed(const CascArgs& A, const v4u* rows, uint32_t last,
+                                                             const uint32_t* __restrict__ src_of, uint32_t pb)
+{
+    using LL = MatLines<K, COL>;
+    constexpr int NR = LL::NR, NL = NR + COL, R = MatrixShape<K, COL>::R, MX = COL > R ? COL : R;
+    static_assert(K >= 2 * COL && K <= 16 && NL <= 8 && MX <= 4, "the cascade kernels' shapes");
+    const uint32_t t = pb * kBlock + threadIdx.x; // (XCD-swizzled: a group's lanes share one L2)
+    if (t >= A.total)
+        return;
+    const uint32_t g = fdiv(t, A.divQC);
+    const uint32_t rem = t - g * A.divQC.d;
+    const uint32_t q = fdiv(rem, A.divC);
+    const uint32_t j = rem - q * A.divC.d;
+    const uint32_t C = A.C;
+    const uint32_t hv = (uint32_t)A.present[2 * g] & LL::KM, er = ~hv & LL::KM;
+    const uint32_t pp = (uint32_t)A.parity_present[g];
+    uint32_t e = er; // slot q: the q-th erased segment
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        e = (uint32_t)i < q ? e & (e - 1u) : e;
+    for (uint32_t i = 3; i < q; ++i)
+        e &= e - 1u;
+    if (!e)
+        return;
+    const uint32_t tgt = (uint32_t)__ffs((int)e) - 1, tb = 1u << tgt;
+    const uint32_t r = tgt / COL, c = tgt - r * COL;
+    const uint32_t rm = (LL::ROW << (r * COL)) & LL::KM, cm = (LL::COL0 << c) & LL::KM;
+    const bool row_fires = r < (uint32_t)NR && ((pp >> r) & 1u) && (rm & er) == tb && (rm & hv);
+    const bool col_fires = ((pp >> (NR + c)) & 1u) && (cm & er) == tb && (cm & hv);
+    const uint32_t* so = src_of + (size_t)g * (K + NL);
+    const v4u* pool = rows + j;
+    v4u* slot0 = A.out_sh + (size_t)g * A.E * C + j;
+    v4u* dst = slot0 + (size_t)q * C;
+    if (row_fires || col_fires) { // single level
+        const uint32_t l = row_fires ? r : NR + c;
+        const uint32_t first = row_fires ? r * COL : c, stride = row_fires ? 1u : (uint32_t)COL;
+        const uint32_t count = row_fires ? min((uint32_t)COL, K - r * COL) : (K - c + COL - 1) / COL;
+        const v4u* src[MX + 1];
+        bool use[MX];
+        src[MX] = pool_row(pool, so, K + l, last, C);
+#pragma unroll
+        for (int u = 0; u < MX; ++u) {
+            const uint32_t i = first + u * stride;
+            use[u] = (uint32_t)u < count && i != tgt;
+            src[u] = pool_row(pool, so, use[u] ? i : K + l, last, C);
+        }
+        v4u acc = ld16(src[MX]);
+        v4u mv[MX];
+#pragma unroll
+        for (int u = 0; u < MX; ++u)
+            mv[u] = ld16(src[u]);
+#pragma unroll
+        for (int u = 0; u < MX; ++u)
+            acc ^= use[u] ? mv[u] : v4u{0, 0, 0, 0};
+        st16(dst, acc);
+        return;
+    }
+    cascade_dense_tail_indexed(A, LL{}, NL, hv, er, pp, tgt, pool, so, K, last, slot0, dst);
+}
+
+template <int K, int COL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_matrix_indexed(
+    CascArgs A, rfec_kmask M, uint32_t n_hr, uint32_t every, uint32_t npay8, const v4u* rows, uint32_t last,
+    const uint32_t* __restrict__ src_of)
+{
+    uint32_t hb = 0, pb = 0;
+    if (header_block_xcd(n_hr, every, npay8, &hb, &pb)) // the checker blocks: the tables only, never a payload row
+        matrix_check_block<K, COL>(A, M, BatchHdrs{A, M.plan}, hb);
+    else
+        matrix_payload_block_indexed<K, COL>(A, rows, last, src_of, pb);
+}
+
 // The batch layout -> packed matrix records (rfec_pack_erasures_matrix): one
 // lane per (group, 16-byte chunk of the record), so every byte of a record --
 // masks, slots, zeros and padding -- leaves in whole 16-byte stores (slots
@@ -962,6 +1112,47 @@ int rfec_launch_recover_packed_matrix(const rfec_kmask* M, uint32_t groups, uint
     default: break;
     }
 #undef RFEC_MP
+    return (int)hipGetLastError();
+}
+
+// rfec_recover_indexed_matrix_out (rfec_recover_indexed_matrix.c): one launch of k_decode_matrix_indexed, no
+// workspace.  n_rows == 0 (no slot can be present): the checker blocks alone, with zero payload lanes -- they
+// still write recovered, out_hdr and out_index, and no row is dereferenced.
+int rfec_launch_recover_indexed_matrix(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                       const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of,
+                                       const rfec_hdr* hdr, const uint64_t* present, const rfec_hdr* meta,
+                                       const uint16_t* fsize, const uint64_t* parity_present, uint64_t* recovered,
+                                       const rfec_dense_out* out, void* stream)
+{
+    const rfec_kplan& P = M->plan;
+    const uint32_t cd = capacity ? (capacity + 15) / 16 : 1, E = out ? out->per_group : 0;
+    if (!rfec_packed_matrix_col(&P) || !groups || !stride || stride % 16 || capacity > stride || !E || E > P.k ||
+        (uint64_t)groups * E * cd >= (1ull << 31) || (uint64_t)groups * kCheckLanes >= (1ull << 32))
+        return (int)hipErrorInvalidValue;
+    CascArgs A = {}; // (no shards, no parity, no workspace: the payload lanes read the pool through src_of)
+    A.hdr_dw = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(hdr)); // dense output: hdr is only read
+    A.meta_dw = reinterpret_cast<const uint32_t*>(meta);
+    A.fsize = fsize, A.present = present, A.parity_present = parity_present, A.recovered = recovered;
+    A.out_sh = reinterpret_cast<v4u*>(out->shards);
+    A.out_hdr_dw = reinterpret_cast<uint32_t*>(out->hdr);
+    A.out_index = out->index;
+    A.E = E, A.C = stride / 16, A.capacity = capacity;
+    casc_lanes(&A, groups, E, cd);
+    if (!n_rows)
+        A.total = 0;
+    const Rounds8 g = casc_dense_grid(A);
+#define RFEC_MI(KK, CC)                                                                                           \
+    case KK:                                                                                                      \
+        rfec_set_indexed_path(3u | (uint32_t)KK << 8);                                                            \
+        RFEC_LAUNCH((k_decode_matrix_indexed<KK, CC>), dim3(g.grid), dim3(kBlock), 0,                             \
+                    reinterpret_cast<hipStream_t>(stream), A, *M, g.hdr_rounds, g.every, g.npay8,                 \
+                    reinterpret_cast<const v4u*>(rows), n_rows ? n_rows - 1 : 0u, src_of);                        \
+        break;
+    switch (P.k) {
+        RFEC_MATRIX_SHAPES(RFEC_MI)
+    default: break;
+    }
+#undef RFEC_MI
     return (int)hipGetLastError();
 }
 

@@ -141,6 +141,7 @@ struct FusedArgs {
 
 void rfec_set_path(uint32_t path);
 #define RFEC_TAG(kind, arg) rfec_set_path(RFEC_PATH(kind, arg)) // the dispatch tag, kept in rfec_kernels.hip
+void rfec_set_indexed_path(uint32_t path); // rfec_indexed_last_path's tag (rfec_internal.h), kept there too
 
 // rfec_encode.hip: a row layout of rows of col <= 16 (rsrc_ok: a wave's groups fit one buffer descriptor), the
 // full matrix plan of k = 6..16, any plan

@@ -187,10 +187,21 @@ int rfec_launch_recover_indexed(const rfec_kmask* M, uint32_t groups, uint32_t s
                                 const uint64_t* present, const rfec_hdr* meta, const uint16_t* fsize,
                                 const uint64_t* parity_present, uint64_t* recovered, void* ws, void* stream,
                                 unsigned flags, const rfec_dense_out* out);
-/* Which kernels the calling thread's last rfec_launch_recover_indexed took (host-side, thread-local, for tests;
- * apart from rfec_last_path, whose kinds are a closed table): 0 none yet, 1 | K << 8 one launch of
- * k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8 k_peel_lds +
- * k_recover_indexed<MAXC, ...> (MAXC = 4, 8). */
+/* rfec_recover_indexed_matrix_out (rfec_recover_indexed_matrix.c, kernel in rfec_cascade.hip): the same decode for
+ * the sender's full row + column plans of k = 6..16 (rfec_packed_matrix_col != 0) in one launch of
+ * k_decode_matrix_indexed<k, col>, no workspace; with n_rows == 0 the checker blocks alone.  The caller has checked
+ * what rfec_launch_recover_indexed's has, the plan's shape, and groups * 4 < 2^32 (the checker's lanes) in place of
+ * the header lanes; hipErrorInvalidValue otherwise.  No flags: rfec_set_tuning does not reach this call. */
+int rfec_launch_recover_indexed_matrix(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                       const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of,
+                                       const rfec_hdr* hdr, const uint64_t* present, const rfec_hdr* meta,
+                                       const uint16_t* fsize, const uint64_t* parity_present, uint64_t* recovered,
+                                       const rfec_dense_out* out, void* stream);
+/* Which kernels the calling thread's last rfec_launch_recover_indexed or rfec_launch_recover_indexed_matrix took
+ * (host-side, thread-local, for tests; apart from rfec_last_path, whose kinds are a closed table): 0 none yet,
+ * 1 | K << 8 one launch of k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8
+ * k_peel_lds + k_recover_indexed<MAXC, ...> (MAXC = 4, 8), 3 | K << 8 one launch of k_decode_matrix_indexed<K, col>
+ * (K = 6..16; rfec_launch_recover_indexed_matrix only). */
 uint32_t rfec_indexed_last_path(void);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */

@@ -9,7 +9,9 @@
 //      rfec_cascade.hip;
 //    * otherwise (and RFEC_TUNE_GENERIC): the peel and the replay of rfec_peel.hip;
 //  recover through a slot map over a row pool (rfec_launch_recover_indexed, dense output only): row layouts in
-//  one launch (rfec_fused.hip), every other plan the peel and an indexed replay (rfec_peel.hip).
+//  one launch (rfec_fused.hip), every other plan the peel and an indexed replay (rfec_peel.hip).  (The sender's
+//  matrix plans in one launch are an entry point of their own, rfec_launch_recover_indexed_matrix in
+//  rfec_cascade.hip: this dispatch does not pick it.)
 #include "rfec_families.h"
 
 static thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
@@ -30,6 +32,7 @@ bool rfec_timing_take(hipEvent_t* start, hipEvent_t* stop)
 }
 
 void rfec_set_path(uint32_t path) { t_path = path; }
+void rfec_set_indexed_path(uint32_t path) { t_indexed_path = path; }
 
 namespace {
 

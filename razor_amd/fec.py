@@ -258,6 +258,8 @@ _SIGS = {
                                            C.c_uint32, C.c_uint16, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "rfec_recover_indexed_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32,
                                            _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
+    "rfec_recover_indexed_matrix_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                                  C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "rfec_host_send_frames": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
@@ -548,6 +550,16 @@ class Native:
                                                       src_of, hdr, present, meta, fec_size, parity_present, recovered,
                                                       per_group, out_shards, out_hdr, out_index, workspace, stream),
                     "rfec_recover_indexed_out")
+
+    def recover_indexed_matrix_out(self, plan, groups, stride, capacity, rows, n_rows, src_of, hdr, present, meta,
+                                   fec_size, parity_present, recovered, per_group, out_shards, out_hdr, out_index,
+                                   stream=None):
+        """rfec_recover_indexed_matrix_out: recover_indexed_out for the sender's full row + column plans of
+        k = 6..16 (packed_matrix_stride(plan, 1) != 0) in one launch, without a workspace."""
+        self._check(self.lib.rfec_recover_indexed_matrix_out(C.byref(as_plan(plan)), groups, stride, capacity, rows,
+                                                             n_rows, src_of, hdr, present, meta, fec_size,
+                                                             parity_present, recovered, per_group, out_shards, out_hdr,
+                                                             out_index, stream), "rfec_recover_indexed_matrix_out")
 
     # -- sender staging (host memory) -------------------------------------------
     def sender_init(self):

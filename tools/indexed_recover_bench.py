@@ -25,6 +25,10 @@ timed work each:
     decode_b         rfec_recover_indexed_out alone, on regroup_index's tables: what the gather costs the decode
     decode_b_generic the same under RFEC_TUNE_GENERIC (k_peel_lds + k_recover_indexed); row layouts only, where
                      the default is the fused k_decode_rows_indexed
+    decode_b_matrix  rfec_recover_indexed_matrix_out alone (one launch of k_decode_matrix_indexed, no workspace), on
+                     the same tables; the sender's full matrix plans only (c3full), where decode_b is the peel + replay
+    chain_b_matrix   rfec_wire_regroup_index + rfec_recover_indexed_matrix_out
+decode_b_matrix's four outputs are compared with decode_b's before anything is timed ("matrix_outputs_equal").
 Each variant reports mean / median / min / max / std over its repetitions: the
 spread the comparison is read against.  Payload bytes moved per chain (derived):
 A copies filled rows x 16 CD twice (read + write), then the decode reads its
@@ -136,6 +140,19 @@ def main() -> int:
             finally:
                 lib.set_tuning(0)
 
+        def decode_b_matrix():
+            for w in wins:
+                d, t = w.dec_b, w.tab
+                lib.recover_indexed_matrix_out(plan, w.G, P, S, w.payload.data_ptr(), w.N, t["src_of"].data_ptr(),
+                                               *(t[key].data_ptr() for key in ("hdr", "present", "meta", "fec_size",
+                                                                               "parity_present")),
+                                               d["recovered"].data_ptr(), E, d["out_shards"].data_ptr(),
+                                               d["out_hdr"].data_ptr(), d["out_index"].data_ptr(), st)
+
+        def chain_b_matrix():
+            regroup_b()
+            decode_b_matrix()
+
         def chain_a():
             regroup_a()
             decode_a()
@@ -171,6 +188,32 @@ def main() -> int:
         variants = {"chain_a": chain_a, "chain_b": chain_b, "decode_a": decode_a, "decode_b": decode_b}
         if paths["default"] != paths["generic"]:
             variants["decode_b_generic"] = decode_b_generic
+        matrix = lib.packed_matrix_stride(plan, 1) != 0  # the plans rfec_recover_indexed_matrix_out takes
+        matrix_equal = None
+        if matrix:  # its four outputs against decode_b's (rfec_recover_indexed_out, default selection)
+            regroup_b()
+            decode_b()
+            torch.cuda.synchronize(dev)
+            ref = [{key: t.clone() for key, t in w.dec_b.items()} for w in wins]
+            for w in wins:
+                for t in w.dec_b.values():
+                    t.fill_(0x3C)
+            decode_b_matrix()
+            paths["matrix"] = hex(int(path()))
+            torch.cuda.synchronize(dev)
+            matrix_equal = True
+            for w, a in zip(wins, ref):
+                b = w.dec_b
+                ok = a["out_index"] != 0xFF
+                matrix_equal &= bool(torch.equal(a["recovered"], b["recovered"]) and
+                                     torch.equal(a["out_index"], b["out_index"]) and
+                                     torch.equal(a["out_hdr"][ok], b["out_hdr"][ok]) and
+                                     torch.equal(a["out_shards"][ok][:, :16 * cd], b["out_shards"][ok][:, :16 * cd]) and
+                                     bool((b["out_shards"][:, :, 16 * cd:] == 0x3C).all()))
+            del ref
+            assert matrix_equal, "rfec_recover_indexed_matrix_out differs from rfec_recover_indexed_out"
+            variants["decode_b_matrix"] = decode_b_matrix
+            variants["chain_b_matrix"] = chain_b_matrix
 
         def run(steps, keep):
             ev = {v: [] for v in variants}
@@ -221,6 +264,14 @@ def main() -> int:
             line["fused_over_generic"] = round(float(us["decode_b"].mean() / g_us.mean()), 4)
             line["fused_max_below_generic_min"] = bool(us["decode_b"].max() < g_us.min())
             line["fused_p95_below_generic_p05"] = below(us["decode_b"], g_us)
+        if matrix:  # the bar: the new decode's 95th percentile below decode_b's 5th
+            m_us = us["decode_b_matrix"]
+            line["matrix_outputs_equal"] = matrix_equal
+            line["matrix_over_decode_b"] = round(float(m_us.mean() / us["decode_b"].mean()), 4)
+            line["matrix_over_decode_a"] = round(float(m_us.mean() / us["decode_a"].mean()), 4)
+            line["matrix_p95_below_decode_b_p05"] = below(m_us, us["decode_b"])
+            line["chain_matrix_over_chain_b"] = round(float(us["chain_b_matrix"].mean() / b_us.mean()), 4)
+            line["chain_matrix_p95_below_chain_b_p05"] = below(us["chain_b_matrix"], b_us)
         text = json.dumps(line)
         print(text, flush=True)
         if args.out:
