@@ -2,6 +2,13 @@
 // records' packer and decode, the matrix decode through a slot map over a row pool, and their launchers;
 // rfec_kernels.hip picks the cascade decode (rfec_launch_recover[_out]), rfec_packed_matrix.c calls the packed
 // records' shims, rfec_recover_indexed_matrix.c the indexed matrix decode's.
+//
+// One copy of each piece: the replay and the dense tail take the received rows as a row source (BatchRows: the
+// batch layout; PoolRows: a row pool through the slot map), the three matrix kernels share matrix_payload_block
+// (NoPool or PoolRows) and, with the generic kernels, cascade_check_block and casc_lane; casc_out_args fills the
+// dense-output arguments for the three launch paths.  Only the dependency closure over a schedule stands twice
+// (k_decode_cascade and cascade_dense_tail).  The batch kernels' code is sensitive to the form of such sharing,
+// not only to its content: DESIGN 7.13 lists the forms that changed it, and tools/kernel_compare.py is the check.
 #include "rfec_families.h"
 
 namespace {
@@ -93,6 +100,19 @@ __device__ CSched cascade_schedule(const Lines& LL, uint32_t NL, MT have, uint64
 __device__ __forceinline__ uint32_t cs_slot(uint32_t E, uint64_t erased, uint32_t i)
 {
     return E ? (uint32_t)__popcll(erased & ((1ull << i) - 1ull)) : i;
+}
+
+// payload lane t: (group, output slot q, chunk column j)
+struct CascLane {
+    uint32_t g, q, j;
+};
+
+__device__ __forceinline__ CascLane casc_lane(const CascArgs& A, uint32_t t)
+{
+    const uint32_t g = fdiv(t, A.divQC);
+    const uint32_t rem = t - g * A.divQC.d;
+    const uint32_t q = fdiv(rem, A.divC);
+    return CascLane{g, q, rem - q * A.divC.d};
 }
 
 // Where a checker reads a group's masks and a step's header bytes (step =
@@ -205,11 +225,32 @@ struct LdsLines {
     __device__ uint64_t mask(uint32_t l) const { return lmask[l]; }
 };
 
-template <class Lines>
+// Where the replay reads a received member's chunk and a line's parity chunk (the chunk column folded into the
+// pointers): the batch layout (grp: the group's segment 0, par: its parity line 0), or a row pool through the
+// group's K + NL words of the slot map (member i in row so[i], parity line l in row so[K + l], clamped: pool_row).
+struct BatchRows {
+    static constexpr bool kPool = false;
+    const v4u *grp, *par;
+    uint32_t C;
+};
+
+struct PoolRows {
+    static constexpr bool kPool = true;
+    const v4u* pool;
+    const uint32_t* __restrict__ so;
+    uint32_t K, last, C;
+};
+
+// (the matrix kernels over the batch layout: no pool)
+struct NoPool {
+    static constexpr bool kPool = false;
+};
+
+template <class Rows, class Lines>
 __device__ __forceinline__ v4u cascade_replay(const CSched& S, uint32_t need, uint32_t ss, uint64_t erased,
-                                              const v4u* grp, const v4u* par, v4u* slot0, uint32_t E, uint32_t C,
-                                              const Lines& LL)
+                                              const Rows& RW, v4u* slot0, uint32_t E, const Lines& LL)
 {
+    const uint32_t C = RW.C;
     v4u res = {0, 0, 0, 0};
 #pragma unroll 1
     for (uint32_t s = 0; s < 8; ++s) {
@@ -217,14 +258,24 @@ __device__ __forceinline__ v4u cascade_replay(const CSched& S, uint32_t need, ui
             continue;
         const uint32_t l = cs_line(S, s), t = cs_tg(S, s), ln = LL.rec(l);
         const uint32_t first = ln & 0xff, stride = (ln >> 8) & 0xff, count = (ln >> 16) & 0xff;
-        v4u acc = ld16(par + (size_t)l * C);
-        v4u mv[4];
+        v4u acc, mv[4];
+        if constexpr (Rows::kPool)
+            acc = ld16(pool_row(RW.pool, RW.so, RW.K + l, RW.last, C));
+        else
+            acc = ld16(RW.par + (size_t)l * C);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t i = first + u * stride;
             mv[u] = v4u{0, 0, 0, 0};
-            if ((uint32_t)u < count && i != t)
-                mv[u] = ld16(((erased >> i) & 1ull) ? slot0 + (size_t)cs_slot(E, erased, i) * C : grp + (size_t)i * C);
+            if ((uint32_t)u < count && i != t) {
+                // (the address arithmetic stands in the ternary's arm: a call there changes the batch kernels' code)
+                if constexpr (Rows::kPool)
+                    mv[u] = ld16(((erased >> i) & 1ull) ? slot0 + (size_t)cs_slot(E, erased, i) * C
+                                                        : pool_row(RW.pool, RW.so, i, RW.last, C));
+                else
+                    mv[u] = ld16(((erased >> i) & 1ull) ? slot0 + (size_t)cs_slot(E, erased, i) * C
+                                                        : RW.grp + (size_t)i * C);
+            }
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -382,31 +433,33 @@ __device__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const
     return cs_pack(X);
 }
 
-// (the batch layout's header arrays)
-template <typename MT, int LPG, bool kTasks, class Lines>
-__device__ __forceinline__ v4u cascade_check_lanes(const CascArgs& A, const rfec_kmask& M, const Lines& LL, uint32_t g,
-                                                   bool live, uint32_t s, uint32_t base)
-{
-    return cascade_check_lanes<MT, LPG, kTasks>(A, M, LL, BatchHdrs{A, M.plan}, g, live, s, base);
-}
-
-// The checker kernel: LPG = 4 lanes per group (16 groups per wave: the
-// schedule's instruction stream is shared by a wave's groups, so fewer lanes
-// per group means fewer waves; one round of loads covers up to 4 steps, i.e.
-// up to 4 erasures recovered).  The group's 16-byte schedule record goes to
-// the workspace for the payload kernel.
+// The checker, LPG = 4 lanes per group (16 groups per wave: the schedule's
+// instruction stream is shared by a wave's groups, so fewer lanes per group
+// means fewer waves; one round of loads covers up to 4 steps, i.e. up to 4
+// erasures recovered).
 constexpr int kCheckLanes = 4;
 
+// Checker block b: lane -> (group, step s), the group's lanes from `base` of
+// the wave; kTasks: the group's 16-byte schedule record and the slots' task
+// words go to the workspace for the payload kernel.
+template <typename MT, bool kTasks, class Lines, class Hdrs>
+__device__ __forceinline__ void cascade_check_block(const CascArgs& A, const rfec_kmask& M, const Lines& LL,
+                                                    const Hdrs& HS, uint32_t b)
+{
+    const uint32_t gt = b * kBlock + threadIdx.x;
+    const uint32_t g = gt / kCheckLanes, s = gt % kCheckLanes;
+    const bool live = g < A.groups;
+    const v4u r = cascade_check_lanes<MT, kCheckLanes, kTasks>(A, M, LL, HS, live ? g : 0u, live, s,
+                                                             (threadIdx.x & (kWave - 1)) & ~(uint32_t)(kCheckLanes - 1));
+    if (kTasks && live && s == 0)
+        *reinterpret_cast<v4u*>(A.ws + (size_t)g * A.ws_stride) = r;
+}
+
+// The checker kernel of the in-place decode.
 template <typename MT>
 __global__ __launch_bounds__(kBlock) void k_cascade_check(CascArgs A, rfec_kmask M)
 {
-    const uint32_t gt = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t g = gt / kCheckLanes, s = gt % kCheckLanes;
-    const bool live = g < A.groups;
-    const v4u r = cascade_check_lanes<MT, kCheckLanes, true>(A, M, KArgLines{M}, live ? g : 0u, live, s,
-                                                       (threadIdx.x & (kWave - 1)) & ~(uint32_t)(kCheckLanes - 1));
-    if (live && s == 0)
-        *reinterpret_cast<v4u*>(A.ws + (size_t)g * A.ws_stride) = r;
+    cascade_check_block<MT, true>(A, M, KArgLines{M}, BatchHdrs{A, M.plan}, blockIdx.x);
 }
 
 // The payload kernel: lane (group, slot, chunk column) reads its slot's task
@@ -426,10 +479,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const uint32_t t = xcd_block(blockIdx.x, gridDim.x) * kBlock + threadIdx.x;
     if (t >= A.total)
         return;
-    const uint32_t g = fdiv(t, A.divQC);
-    const uint32_t rem = t - g * A.divQC.d;
-    const uint32_t q = fdiv(rem, A.divC);
-    const uint32_t j = rem - q * A.divC.d;
+    const auto [g, q, j] = casc_lane(A, t);
     const uint32_t K = P.k, NL = P.n_lines, C = A.C;
     const uint8_t* wg = A.ws + (size_t)g * A.ws_stride;
     const uint32_t task = reinterpret_cast<const uint32_t*>(wg + 16)[q];
@@ -468,7 +518,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     for (int s = 0; s < 8; ++s)
         if ((uint32_t)s < S.n && cs_tg(S, s) == tgt)
             ss = s;
-    uint32_t need = 1u << ss;
+    uint32_t need = 1u << ss; // (the closure is cascade_dense_tail's, kept twice deliberately: DESIGN 7.13)
 #pragma unroll 1
     for (int s = (int)ss; s >= 0; --s) {
         if (!((need >> s) & 1u))
@@ -478,17 +528,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             if ((dm >> cs_tg(S, s2)) & 1ull)
                 need |= 1u << s2;
     }
-    st16(dst, cascade_replay(S, need, ss, erased, grp, par, slot0, A.E, C, LdsLines{lplan, lmask}));
+    st16(dst, cascade_replay(S, need, ss, erased, BatchRows{grp, par, C}, slot0, A.E, LdsLines{lplan, lmask}));
 }
 
 // A dense payload lane whose target no line recovers at once (a cascade):
 // the group's mask schedule (cascade_schedule without the header checks),
 // the steps the target's step reads, transitively, replayed in registers.
-// (SL: the schedule's masks -- kernel arguments or constants; LL: the replay's)
-template <typename MT, class SLines, class Lines>
+// (SL: the schedule's masks -- kernel arguments or constants; LL: the replay's; RW: the received rows)
+template <typename MT, class SLines, class Rows, class Lines>
 __device__ __forceinline__ void cascade_dense_tail(const CascArgs& A, const SLines& SL, uint32_t NL, uint64_t have,
-                                                   uint64_t erased, uint64_t ppm, uint32_t tgt, const v4u* grp,
-                                                   const v4u* par, v4u* slot0, v4u* dst, const Lines& LL)
+                                                   uint64_t erased, uint64_t ppm, uint32_t tgt, const Rows& RW,
+                                                   v4u* slot0, v4u* dst, const Lines& LL)
 {
     const CSched S = cascade_schedule<MT>(SL, NL, (MT)have, ppm, 0u, (MT)erased, A.E);
     uint32_t ss = 8;
@@ -498,7 +548,7 @@ __device__ __forceinline__ void cascade_dense_tail(const CascArgs& A, const SLin
             ss = s;
     if (ss == 8)
         return; // not recoverable
-    uint32_t need = 1u << ss;
+    uint32_t need = 1u << ss; // (the closure is k_decode_cascade's, kept twice deliberately: DESIGN 7.13)
 #pragma unroll 1
     for (int s = (int)ss; s >= 0; --s) {
         if (!((need >> s) & 1u))
@@ -508,7 +558,7 @@ __device__ __forceinline__ void cascade_dense_tail(const CascArgs& A, const SLin
             if ((dm >> cs_tg(S, s2)) & 1ull)
                 need |= 1u << s2;
     }
-    st16(dst, cascade_replay(S, need, ss, erased, grp, par, slot0, A.E, A.C, LL));
+    st16(dst, cascade_replay(S, need, ss, erased, RW, slot0, A.E, LL));
 }
 
 // Dense output, one launch: rounds of 8 checker blocks spread over the grid
@@ -535,11 +585,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 {
     uint32_t hb = 0, pb = 0;
     if (header_block_xcd(n_hr, every, npay8, &hb, &pb)) { // (checker blocks XCD-aligned with the payload sweep)
-        const uint32_t gt = hb * kBlock + threadIdx.x;
-        const uint32_t g = gt / kCheckLanes, s = gt % kCheckLanes;
-        const bool live = g < A.groups;
-        cascade_check_lanes<MT, kCheckLanes, false>(A, M, KArgLines{M}, live ? g : 0u, live, s,
-                                                    (threadIdx.x & (kWave - 1)) & ~(uint32_t)(kCheckLanes - 1));
+        cascade_check_block<MT, false>(A, M, KArgLines{M}, BatchHdrs{A, M.plan}, hb);
         return;
     }
     __shared__ uint32_t lplan[RFEC_MAX_LINES];
@@ -551,10 +597,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const uint32_t t = pb * kBlock + threadIdx.x; // (XCD-swizzled: a group's lanes share one L2)
     if (t >= A.total)
         return;
-    const uint32_t g = fdiv(t, A.divQC);
-    const uint32_t rem = t - g * A.divQC.d;
-    const uint32_t q = fdiv(rem, A.divC);
-    const uint32_t j = rem - q * A.divC.d;
+    const auto [g, q, j] = casc_lane(A, t);
     const uint32_t K = P.k, NL = P.n_lines, C = A.C;
     // (MT: 32-bit masks for k <= 32, the low words of present / parity_present)
     constexpr uint32_t MB = 8 * sizeof(MT);
@@ -606,7 +649,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         st16(dst, acc);
         return;
     }
-    cascade_dense_tail<MT>(A, KArgLines{M}, NL, have, erased, ppm, tgt, grp, par, slot0, dst, LdsLines{lplan, lmask});
+    cascade_dense_tail<MT>(A, KArgLines{M}, NL, have, erased, ppm, tgt, BatchRows{grp, par, A.C}, slot0, dst,
+                           LdsLines{lplan, lmask});
 }
 
 // The sender's full matrix plans (rows of COL consecutive segments, then the
@@ -623,7 +667,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 template <int K, int COL>
 struct MatLines {
     using Sh = MatrixShape<K, COL>;
-    static constexpr int NR = Sh::n_rows();
+    static constexpr int NR = Sh::n_rows(), NL = NR + COL, MX = COL > Sh::R ? COL : Sh::R; // MX: a line's most members
+    static_assert(K >= 2 * COL && K <= 16 && NL <= 8 && MX <= 4, "the cascade kernels' shapes");
     static constexpr uint32_t KM = (1u << K) - 1u, ROW = (1u << COL) - 1u;
     static constexpr uint32_t col0()
     {
@@ -649,31 +694,19 @@ struct MatLines {
     __device__ uint32_t nl(uint32_t) const { return NR + COL; }
 };
 
-// The kernel's two halves, shared with the packed-record sibling below (HS:
-// where the masks and the checker's header bytes come from).
-template <int K, int COL, class Hdrs>
-__device__ __forceinline__ void matrix_check_block(const CascArgs& A, const rfec_kmask& M, const Hdrs& HS, uint32_t hb)
-{
-    const uint32_t gt = hb * kBlock + threadIdx.x;
-    const uint32_t g = gt / kCheckLanes, s = gt % kCheckLanes;
-    const bool live = g < A.groups;
-    cascade_check_lanes<uint32_t, kCheckLanes, false>(A, M, MatLines<K, COL>{}, HS, live ? g : 0u, live, s,
-                                                      (threadIdx.x & (kWave - 1)) & ~(uint32_t)(kCheckLanes - 1));
-}
-
-template <int K, int COL, class Hdrs>
-__device__ __forceinline__ void matrix_payload_block(const CascArgs& A, const Hdrs& HS, uint32_t pb)
+// The payload half of the matrix kernels, shared by the three of them (HS: where the masks come from; PL: NoPool
+// for the batch layout, or the pool and the slot map -- the PoolRows of group 0 at chunk column 0).  The batch
+// layout's and the pool's lanes differ in where the group's rows are, in the loads of a line that fires at once
+// and in the row source they hand to the cascade tail.
+template <int K, int COL, class Hdrs, class Pool>
+__device__ __forceinline__ void matrix_payload_block(const CascArgs& A, const Hdrs& HS, const Pool& PL, uint32_t pb)
 {
     using LL = MatLines<K, COL>;
-    constexpr int NR = LL::NR, NL = NR + COL, R = MatrixShape<K, COL>::R, MX = COL > R ? COL : R;
-    static_assert(K >= 2 * COL && K <= 16 && NL <= 8 && MX <= 4, "the cascade kernels' shapes");
+    constexpr int NR = LL::NR, NL = LL::NL, MX = LL::MX;
     const uint32_t t = pb * kBlock + threadIdx.x; // (XCD-swizzled: a group's lanes share one L2)
     if (t >= A.total)
         return;
-    const uint32_t g = fdiv(t, A.divQC);
-    const uint32_t rem = t - g * A.divQC.d;
-    const uint32_t q = fdiv(rem, A.divC);
-    const uint32_t j = rem - q * A.divC.d;
+    const auto [g, q, j] = casc_lane(A, t);
     const uint32_t C = A.C;
     const uint32_t hv = (uint32_t)HS.present(g) & LL::KM, er = ~hv & LL::KM;
     const uint32_t pp = (uint32_t)HS.parity_present(g);
@@ -690,32 +723,67 @@ __device__ __forceinline__ void matrix_payload_block(const CascArgs& A, const Hd
     const uint32_t rm = (LL::ROW << (r * COL)) & LL::KM, cm = (LL::COL0 << c) & LL::KM;
     const bool row_fires = r < (uint32_t)NR && ((pp >> r) & 1u) && (rm & er) == tb && (rm & hv);
     const bool col_fires = ((pp >> (NR + c)) & 1u) && (cm & er) == tb && (cm & hv);
-    const v4u* grp = A.shards + (size_t)g * K * C + j;
-    const v4u* par = A.parity + (size_t)g * NL * C + j;
+    // the group's rows at chunk column j: in the batch layout (the addresses formed here, not in a row source
+    // handed down: that changes the batch kernels' code), or through the group's words of the map
+    const v4u *grp = nullptr, *par = nullptr;
+    Pool RW = PL;
+    if constexpr (Pool::kPool) {
+        RW.pool += j, RW.so += (size_t)g * (K + NL);
+    } else {
+        grp = A.shards + (size_t)g * K * C + j;
+        par = A.parity + (size_t)g * NL * C + j;
+    }
     v4u* slot0 = A.out_sh + (size_t)g * A.E * C + j;
     v4u* dst = slot0 + (size_t)q * C;
     if (row_fires || col_fires) { // single level
         const uint32_t l = row_fires ? r : NR + c;
         const uint32_t first = row_fires ? r * COL : c, stride = row_fires ? 1u : (uint32_t)COL;
         const uint32_t count = row_fires ? min((uint32_t)COL, K - r * COL) : (K - c + COL - 1) / COL;
-        v4u acc = ld16(par + (size_t)l * C);
-        // members through a descriptor over the first active lane's group (see k_decode_cascade_dense)
-        const uint32_t gb = (uint32_t)__builtin_amdgcn_readfirstlane((int)g); // lanes' groups ascend
-        const __amdgpu_buffer_rsrc_t rs = wave_rsrc(A.shards + (size_t)gb * K * C);
-        const uint32_t grp0 = ((g - gb) * K * C + j) * 16u;
-        v4u mv[MX];
+        if constexpr (Pool::kPool) {
+            // the rows lie anywhere in the pool: plain 64-bit addresses -- the map words of the wanted slots first,
+            // then the parity and the MX member chunks unconditionally and in flight together; a member that is not
+            // wanted (past the line's end, or the target) re-reads the parity chunk and is XORed as zero
+            const v4u* src[MX + 1];
+            bool use[MX];
+            src[MX] = pool_row(RW.pool, RW.so, K + l, RW.last, C);
 #pragma unroll
-        for (int u = 0; u < MX; ++u) {
-            const uint32_t i = first + u * stride;
-            mv[u] = bld16(rs, (uint32_t)u < count && i != tgt ? grp0 + i * C * 16u : kNoLoad);
+            for (int u = 0; u < MX; ++u) {
+                const uint32_t i = first + u * stride;
+                use[u] = (uint32_t)u < count && i != tgt;
+                src[u] = pool_row(RW.pool, RW.so, use[u] ? i : K + l, RW.last, C);
+            }
+            v4u acc = ld16(src[MX]);
+            v4u mv[MX];
+#pragma unroll
+            for (int u = 0; u < MX; ++u)
+                mv[u] = ld16(src[u]);
+#pragma unroll
+            for (int u = 0; u < MX; ++u)
+                acc ^= use[u] ? mv[u] : v4u{0, 0, 0, 0};
+            st16(dst, acc);
+        } else {
+            v4u acc = ld16(par + (size_t)l * C);
+            // members through a descriptor over the first active lane's group (see k_decode_cascade_dense)
+            const uint32_t gb = (uint32_t)__builtin_amdgcn_readfirstlane((int)g); // lanes' groups ascend
+            const __amdgpu_buffer_rsrc_t rs = wave_rsrc(A.shards + (size_t)gb * K * C);
+            const uint32_t grp0 = ((g - gb) * K * C + j) * 16u;
+            v4u mv[MX];
+#pragma unroll
+            for (int u = 0; u < MX; ++u) {
+                const uint32_t i = first + u * stride;
+                mv[u] = bld16(rs, (uint32_t)u < count && i != tgt ? grp0 + i * C * 16u : kNoLoad);
+            }
+#pragma unroll
+            for (int u = 0; u < MX; ++u)
+                acc ^= mv[u];
+            st16(dst, acc);
         }
-#pragma unroll
-        for (int u = 0; u < MX; ++u)
-            acc ^= mv[u];
-        st16(dst, acc);
         return;
     }
-    cascade_dense_tail<uint32_t>(A, LL{}, NL, hv, er, pp, tgt, grp, par, slot0, dst, LL{});
+    if constexpr (Pool::kPool)
+        cascade_dense_tail<uint32_t>(A, LL{}, NL, hv, er, pp, tgt, RW, slot0, dst, LL{});
+    else
+        cascade_dense_tail<uint32_t>(A, LL{}, NL, hv, er, pp, tgt, BatchRows{grp, par, A.C}, slot0, dst, LL{});
 }
 
 template <int K, int COL>
@@ -725,9 +793,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const BatchHdrs HS{A, M.plan};
     uint32_t hb = 0, pb = 0;
     if (header_block_xcd(n_hr, every, npay8, &hb, &pb)) // the checker blocks, as the generic kernel's
-        matrix_check_block<K, COL>(A, M, HS, hb);
+        cascade_check_block<uint32_t, false>(A, M, MatLines<K, COL>{}, HS, hb);
     else
-        matrix_payload_block<K, COL>(A, HS, pb);
+        matrix_payload_block<K, COL>(A, HS, NoPool{}, pb);
 }
 
 // The same decode from packed matrix records (rfec_recover_packed_matrix_out;
@@ -776,13 +844,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const PackedMatHdrs<K, COL> HS{packed, pk_stride};
     uint32_t hb = 0, pb = 0;
     if (header_block_xcd(n_hr, every, npay8, &hb, &pb))
-        matrix_check_block<K, COL>(A, M, HS, hb);
+        cascade_check_block<uint32_t, false>(A, M, MatLines<K, COL>{}, HS, hb);
     else
-        matrix_payload_block<K, COL>(A, HS, pb);
+        matrix_payload_block<K, COL>(A, HS, NoPool{}, pb);
 }
 
 // The same decode through a slot map over a row pool (rfec_recover_indexed_matrix_out): the checker half is
-// k_decode_matrix_dense's unchanged -- it reads the tables only -- and a payload lane reads member i of its group
+// k_decode_matrix_dense's -- it reads the tables only -- and a payload lane reads member i of its group
 // from row so[i] of the pool and parity line l from row so[K + l] (so: the group's K + NL words of src_of; pool:
 // chunk j of row 0).  The rows lie anywhere in the pool, so no descriptor spans a wave's loads (wave_rsrc / bld16 do
 // not carry over): they are plain 64-bit addresses, as in k_decode_rows_indexed -- the map words of the wanted
@@ -790,144 +858,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 // not wanted (past the line's end, or the target) re-reads the parity chunk and is XORed as zero.  A row index is
 // clamped to `last` = n_rows - 1 before it is used (pool_row).  Only the entries of present members and received
 // parities are read: a line fires, or takes a step of the schedule, with its parity received, and a member that
-// was not received comes from the dense out slot where an earlier step stored it.
-//
-// The replay is a copy of cascade_replay, not a row-source parameter of it: the existing kernels' code stays as
-// it is.
-template <class Lines>
-__device__ __forceinline__ v4u cascade_replay_indexed(const CSched& S, uint32_t need, uint32_t ss, uint64_t erased,
-                                                      const v4u* pool, const uint32_t* __restrict__ so, uint32_t K,
-                                                      uint32_t last, v4u* slot0, uint32_t E, uint32_t C,
-                                                      const Lines& LL)
-{
-    v4u res = {0, 0, 0, 0};
-#pragma unroll 1
-    for (uint32_t s = 0; s < 8; ++s) {
-        if (!((need >> s) & 1u))
-            continue;
-        const uint32_t l = cs_line(S, s), t = cs_tg(S, s), ln = LL.rec(l);
-        const uint32_t first = ln & 0xff, stride = (ln >> 8) & 0xff, count = (ln >> 16) & 0xff;
-        v4u acc = ld16(pool_row(pool, so, K + l, last, C));
-        v4u mv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint32_t i = first + u * stride;
-            mv[u] = v4u{0, 0, 0, 0};
-            if ((uint32_t)u < count && i != t)
-                mv[u] = ld16(((erased >> i) & 1ull) ? slot0 + (size_t)cs_slot(E, erased, i) * C
-                                                    : pool_row(pool, so, i, last, C));
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            acc ^= mv[u];
-        if (s == ss) {
-            res = acc;
-            break;
-        }
-        st16(slot0 + (size_t)cs_slot(E, erased, t) * C, acc);
-    }
-    return res;
-}
-
-// cascade_dense_tail over the pool (MatLines serve both the schedule and the replay)
-template <class Lines>
-__device__ __forceinline__ void cascade_dense_tail_indexed(const CascArgs& A, const Lines& LL, uint32_t NL, uint32_t have,
-                                                           uint32_t erased, uint32_t ppm, uint32_t tgt, const v4u* pool,
-                                                           const uint32_t* __restrict__ so, uint32_t K, uint32_t last,
-                                                           v4u* slot0, v4u* dst)
-{
-    const CSched S = cascade_schedule<uint32_t>(LL, NL, have, ppm, 0u, erased, A.E);
-    uint32_t ss = 8;
-#pragma unroll
-    for (int s = 0; s < 8; ++s)
-        if ((uint32_t)s < S.n && cs_tg(S, s) == tgt)
-            ss = s;
-    if (ss == 8)
-        return; // not recoverable
-    uint32_t need = 1u << ss;
-#pragma unroll 1
-    for (int s = (int)ss; s >= 0; --s) {
-        if (!((need >> s) & 1u))
-            continue;
-        const uint64_t dm = LL.mask(cs_line(S, s)) & erased & ~(1ull << cs_tg(S, s));
-        for (int s2 = 0; s2 < s; ++s2)
-            if ((dm >> cs_tg(S, s2)) & 1ull)
-                need |= 1u << s2;
-    }
-    st16(dst, cascade_replay_indexed(S, need, ss, erased, pool, so, K, last, slot0, A.E, A.C, LL));
-}
-
-template <int K, int COL>
-__device__ __forceinline__ void matrix_payload_block_indexed(const CascArgs& A, const v4u* rows, uint32_t last,
-                                                             const uint32_t* __restrict__ src_of, uint32_t pb)
-{
-    using LL = MatLines<K, COL>;
-    constexpr int NR = LL::NR, NL = NR + COL, R = MatrixShape<K, COL>::R, MX = COL > R ? COL : R;
-    static_assert(K >= 2 * COL && K <= 16 && NL <= 8 && MX <= 4, "the cascade kernels' shapes");
-    const uint32_t t = pb * kBlock + threadIdx.x; // (XCD-swizzled: a group's lanes share one L2)
-    if (t >= A.total)
-        return;
-    const uint32_t g = fdiv(t, A.divQC);
-    const uint32_t rem = t - g * A.divQC.d;
-    const uint32_t q = fdiv(rem, A.divC);
-    const uint32_t j = rem - q * A.divC.d;
-    const uint32_t C = A.C;
-    const uint32_t hv = (uint32_t)A.present[2 * g] & LL::KM, er = ~hv & LL::KM;
-    const uint32_t pp = (uint32_t)A.parity_present[g];
-    uint32_t e = er; // slot q: the q-th erased segment
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        e = (uint32_t)i < q ? e & (e - 1u) : e;
-    for (uint32_t i = 3; i < q; ++i)
-        e &= e - 1u;
-    if (!e)
-        return;
-    const uint32_t tgt = (uint32_t)__ffs((int)e) - 1, tb = 1u << tgt;
-    const uint32_t r = tgt / COL, c = tgt - r * COL;
-    const uint32_t rm = (LL::ROW << (r * COL)) & LL::KM, cm = (LL::COL0 << c) & LL::KM;
-    const bool row_fires = r < (uint32_t)NR && ((pp >> r) & 1u) && (rm & er) == tb && (rm & hv);
-    const bool col_fires = ((pp >> (NR + c)) & 1u) && (cm & er) == tb && (cm & hv);
-    const uint32_t* so = src_of + (size_t)g * (K + NL);
-    const v4u* pool = rows + j;
-    v4u* slot0 = A.out_sh + (size_t)g * A.E * C + j;
-    v4u* dst = slot0 + (size_t)q * C;
-    if (row_fires || col_fires) { // single level
-        const uint32_t l = row_fires ? r : NR + c;
-        const uint32_t first = row_fires ? r * COL : c, stride = row_fires ? 1u : (uint32_t)COL;
-        const uint32_t count = row_fires ? min((uint32_t)COL, K - r * COL) : (K - c + COL - 1) / COL;
-        const v4u* src[MX + 1];
-        bool use[MX];
-        src[MX] = pool_row(pool, so, K + l, last, C);
-#pragma unroll
-        for (int u = 0; u < MX; ++u) {
-            const uint32_t i = first + u * stride;
-            use[u] = (uint32_t)u < count && i != tgt;
-            src[u] = pool_row(pool, so, use[u] ? i : K + l, last, C);
-        }
-        v4u acc = ld16(src[MX]);
-        v4u mv[MX];
-#pragma unroll
-        for (int u = 0; u < MX; ++u)
-            mv[u] = ld16(src[u]);
-#pragma unroll
-        for (int u = 0; u < MX; ++u)
-            acc ^= use[u] ? mv[u] : v4u{0, 0, 0, 0};
-        st16(dst, acc);
-        return;
-    }
-    cascade_dense_tail_indexed(A, LL{}, NL, hv, er, pp, tgt, pool, so, K, last, slot0, dst);
-}
-
+// was not received comes from the dense out slot where an earlier step stored it.  The payload block, the tail and
+// the replay are the batch kernels' own, with PoolRows as their row source.
 template <int K, int COL>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_matrix_indexed(
     CascArgs A, rfec_kmask M, uint32_t n_hr, uint32_t every, uint32_t npay8, const v4u* rows, uint32_t last,
     const uint32_t* __restrict__ src_of)
 {
+    const BatchHdrs HS{A, M.plan}; // (the masks and the checker's header bytes: the tables, as the dense kernel's)
     uint32_t hb = 0, pb = 0;
     if (header_block_xcd(n_hr, every, npay8, &hb, &pb)) // the checker blocks: the tables only, never a payload row
-        matrix_check_block<K, COL>(A, M, BatchHdrs{A, M.plan}, hb);
+        cascade_check_block<uint32_t, false>(A, M, MatLines<K, COL>{}, HS, hb);
     else
-        matrix_payload_block_indexed<K, COL>(A, rows, last, src_of, pb);
+        matrix_payload_block<K, COL>(A, HS, PoolRows{rows, src_of, K, last, A.C}, pb);
 }
 
 // The batch layout -> packed matrix records (rfec_pack_erasures_matrix): one
@@ -1019,6 +962,18 @@ Rounds8 casc_dense_grid(const CascArgs& A)
 
 } // namespace
 
+// the dense-output half of A (out null or per_group 0: in place), with the payload stride and capacity
+void casc_out_args(CascArgs* A, const rfec_dense_out* out, uint32_t stride, uint32_t capacity)
+{
+    const bool dense = out && out->per_group;
+    A->out_sh = dense ? reinterpret_cast<v4u*>(out->shards) : nullptr;
+    A->out_hdr_dw = dense ? reinterpret_cast<uint32_t*>(out->hdr) : nullptr;
+    A->out_index = dense ? out->index : nullptr;
+    A->E = dense ? out->per_group : 0u;
+    A->C = stride / 16;
+    A->capacity = capacity;
+}
+
 // cascade decode, dense: one launch (k_decode_cascade_dense, or k_decode_matrix_dense for the sender's full
 // matrix plans); in place: the checker (schedule records and task words into the workspace), then the payload
 // lanes, Q slots per group (one per possible step)
@@ -1093,12 +1048,7 @@ int rfec_launch_recover_packed_matrix(const rfec_kmask* M, uint32_t groups, uint
     A.shards = const_cast<v4u*>(reinterpret_cast<const v4u*>(shards));
     A.parity = reinterpret_cast<const v4u*>(parity);
     A.recovered = recovered;
-    A.out_sh = reinterpret_cast<v4u*>(out->shards);
-    A.out_hdr_dw = reinterpret_cast<uint32_t*>(out->hdr);
-    A.out_index = out->index;
-    A.E = out->per_group;
-    A.C = stride / 16;
-    A.capacity = capacity;
+    casc_out_args(&A, out, stride, capacity);
     casc_lanes(&A, groups, A.E, capacity ? (capacity + 15) / 16 : 1); // < 2^32 lanes: host-checked
     const Rounds8 g = casc_dense_grid(A);
 #define RFEC_MP(KK, CC)                                                                                           \
@@ -1133,10 +1083,7 @@ int rfec_launch_recover_indexed_matrix(const rfec_kmask* M, uint32_t groups, uin
     A.hdr_dw = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(hdr)); // dense output: hdr is only read
     A.meta_dw = reinterpret_cast<const uint32_t*>(meta);
     A.fsize = fsize, A.present = present, A.parity_present = parity_present, A.recovered = recovered;
-    A.out_sh = reinterpret_cast<v4u*>(out->shards);
-    A.out_hdr_dw = reinterpret_cast<uint32_t*>(out->hdr);
-    A.out_index = out->index;
-    A.E = E, A.C = stride / 16, A.capacity = capacity;
+    casc_out_args(&A, out, stride, capacity);
     casc_lanes(&A, groups, E, cd);
     if (!n_rows)
         A.total = 0;

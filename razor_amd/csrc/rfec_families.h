@@ -174,7 +174,10 @@ void launch_fused_rows(const FusedArgs& F, const PeelArgs& B, const rfec_kmask& 
 void launch_rows_indexed(const v4u* pool, uint32_t last, const uint32_t* src_of, const FusedArgs& F,
                          const PeelArgs& B, const rfec_kmask& M, uint32_t cd, uint32_t col);
 
-// rfec_cascade.hip (matrix: the plan is a full matrix of k = 6..16, a dense output takes k_decode_matrix_dense)
+// rfec_cascade.hip (casc_out_args: the dense-output fields of A, E and the out pointers, from the call's `out` --
+// null or per_group 0: in place -- with C = stride / 16 and the capacity; matrix: the plan is a full matrix of
+// k = 6..16, a dense output takes k_decode_matrix_dense)
+void casc_out_args(CascArgs* A, const rfec_dense_out* out, uint32_t stride, uint32_t capacity);
 void launch_cascade(CascArgs A, const rfec_kmask& M, uint32_t groups, uint32_t cd, void* ws, uint32_t ws_stride,
                     hipStream_t st, bool matrix);
 

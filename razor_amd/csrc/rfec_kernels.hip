@@ -147,9 +147,7 @@ int launch_recover(const rfec_kmask* M, uint32_t groups, uint32_t stride, uint32
         A.shards = sh, A.parity = pp;
         A.hdr_dw = reinterpret_cast<uint32_t*>(hdr), A.meta_dw = reinterpret_cast<const uint32_t*>(meta);
         A.fsize = fsize, A.present = present, A.parity_present = parity_present, A.recovered = recovered;
-        A.out_sh = DO.sh, A.out_hdr_dw = dense ? reinterpret_cast<uint32_t*>(out->hdr) : nullptr;
-        A.out_index = dense ? out->index : nullptr;
-        A.E = DO.E, A.C = C, A.capacity = capacity;
+        casc_out_args(&A, out, stride, capacity);
         launch_cascade(A, *M, groups, cd, ws, B.rec_bytes, st,
                        !(flags & RFEC_KFLAG_MATRIX_GENERIC) && rfec_packed_matrix_col(&P));
         return (int)hipGetLastError();
