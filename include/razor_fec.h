@@ -401,7 +401,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -545,6 +545,74 @@ int rfec_wire_encode_send(const rfec_plan* plan, uint32_t groups, uint32_t strid
                           const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
                           uint8_t* fec_dgram, uint16_t* fec_dlen,
                           uint32_t dstride, void* stream);
+
+/* rfec_wire_encode_send over a send window whose groups have different shapes
+ * (the flex sender closes a group per frame, so k and row x col follow the
+ * frame size), in one launch: the sender-side counterpart of
+ * rfec_wire_regroup_shapes.  The window's member rows lie in shards / hdr /
+ * seg_stamps [n_rows] in any layout, its SIM_FEC stamps in fec_stamps [n_fec];
+ * group g of the call is a descriptor. */
+#define RFEC_SEND_MAX_SHAPES 32
+#define RFEC_SEND_MAX_LINES  512   /* sum of n_lines over the call's plans */
+
+typedef struct {          /* one group of the window; DEVICE array */
+    uint32_t row0;        /* first member row: members are rows row0 .. row0 + k_p - 1 */
+    uint32_t line0;       /* first SIM_FEC index: lines are line0 .. line0 + n_p - 1 */
+    uint32_t shape;       /* index into plans; >= n_plans: the group is skipped */
+    uint32_t reserved;    /* 0 */
+} rfec_send_group;        /* 16 bytes */
+
+/* Equivalence.  For every group g that is not skipped, with p = group[g].shape,
+ * k_p = plans[p].k and n_p = plans[p].n_lines, the call writes byte for byte
+ * what rfec_wire_encode_send(&plans[p], 1, ...) writes for the same rows,
+ * headers and stamps, whole slots: the SIM_SEG slots and lengths of rows
+ * row0 .. row0 + k_p - 1 (seg_dgram / seg_dlen [n_rows]) and the SIM_FEC slots
+ * and lengths of lines line0 .. line0 + n_p - 1 (fec_dgram / fec_dlen
+ * [n_fec]); with the orders, through seg_order[row0 + i] / fec_order[line0 + l]
+ * (permutations of [0, n_rows) / [0, n_fec), each may be NULL).  So a segment
+ * above `capacity` gets length 0 and a zero slot, a refused line likewise, and
+ * a plan without lines frames only segments.
+ * Skipped groups.  A group is skipped when shape >= n_plans, or
+ * row0 + k_p > n_rows, or line0 + n_p > n_fec: it reads nothing and writes
+ * nothing (the device cannot return RFEC_EINVAL for a bad descriptor, so this
+ * is the rule).  Rows and lines that no group covers keep what their slots
+ * held.
+ * Overlap.  Overlapping row or line ranges of two groups are the caller's
+ * fault: the result for those slots is unspecified; nothing is accessed outside
+ * the buffers.
+ * Descriptor order is free and need not follow row order.  A wave takes four
+ * consecutive descriptors: four of one shape run at rfec_wire_encode_send's
+ * rate, a mixed four costs one pass per distinct shape.  So a caller who sorts
+ * the descriptors by shape -- not the rows -- gets full lanes and still gets
+ * the datagrams in send order.
+ * "Slot tails": the shards' bytes from 16 * CD to the stride are not read.
+ * One launch, always: the call is not split, so the 32-bit buffer offsets are
+ * argument checks (RFEC_EINVAL, "split the window"): (n_rows + 4) * stride +
+ * 1280, n_rows * 20, n_rows * dstride, n_fec * dstride, n_fec * 24 and
+ * groups * 16 must each stay below 0xFFFFFFF0.
+ * Checked before any runtime call (RFEC_EINVAL, rfec_last_error names the
+ * argument): plans (NULL, n_plans in [1, RFEC_SEND_MAX_SHAPES], every plan as
+ * for rfec_wire_encode_send with k <= RFEC_MAX_K_ENCODE, the sum of n_lines
+ * <= RFEC_SEND_MAX_LINES); stride / capacity / dstride as for
+ * rfec_wire_encode_send (dstride >= capacity + 49, dstride <= 1280); NULL
+ * pointers (the four SIM_FEC pointers may be NULL when n_fec == 0, each order
+ * always); alignment: 16 bytes shards, seg_dgram and fec_dgram, 4 bytes group,
+ * hdr, both stamp arrays and both orders, 2 bytes seg_dlen and fec_dlen.
+ * groups == 0 touches nothing: every pointer but plans may be NULL.
+ * The call allocates nothing, copies nothing from the host (the plans travel
+ * in the kernel's argument block), does not synchronise and launches only on
+ * `stream`.  The four outputs must not overlap each other or any input (not
+ * checked). */
+int rfec_wire_encode_send_shapes(const rfec_plan* plans, uint32_t n_plans,       /* host */
+                                 uint32_t groups, const rfec_send_group* group,  /* device [groups] */
+                                 uint32_t n_rows, uint32_t n_fec,
+                                 uint32_t stride, uint32_t capacity,
+                                 const uint8_t* shards, const rfec_hdr* hdr,     /* [n_rows] */
+                                 const rfec_seg_stamp* seg_stamps, const uint32_t* seg_order,
+                                 uint8_t* seg_dgram, uint16_t* seg_dlen,         /* [n_rows] */
+                                 const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
+                                 uint8_t* fec_dgram, uint16_t* fec_dlen,         /* [n_fec] */
+                                 uint32_t dstride, void* stream);
 
 /* Parse status (rfec_wire_rec.status). */
 #define RFEC_WIRE_OK 0         /* SIM_SEG / SIM_FEC decoded (a SEG with a bad data length decodes

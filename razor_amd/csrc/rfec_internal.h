@@ -155,6 +155,24 @@ int rfec_launch_wire_encode_send(const rfec_kplan* P, uint32_t groups, uint32_t 
                                  uint32_t seg_rows_out, const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
                                  uint8_t* fec_dgram, uint16_t* fec_dlen, uint32_t fec_rows_out, uint32_t dstride,
                                  void* stream);
+/* rfec_wire_encode_send_shapes's plans as its kernel takes them, in the argument block: the lines of every plan,
+ * shape after shape, one dword each (first | stride << 8 | count << 16: an rfec_line), and per shape
+ * k | n_lines << 8 | the index of its first line << 16. */
+typedef struct {
+    uint32_t n_plans;
+    uint32_t shape[RFEC_SEND_MAX_SHAPES];
+    uint32_t line[RFEC_SEND_MAX_LINES];
+} rfec_send_shapes;
+/* rfec_wire_encode_send_shapes (rfec_wire_fused.c): its one launch.  The caller has checked the plans
+ * (check_plan, their lines' sum) and keeps (n_rows + 4) * stride + 1280, n_rows * 20, n_rows * dstride,
+ * n_fec * dstride, n_fec * 24 and groups * 16 below 0xFFFFFFF0, dstride <= 1280 and stride a multiple of 16;
+ * hipErrorInvalidValue otherwise.  With n_fec == 0 the FEC pointers are not touched. */
+int rfec_launch_wire_encode_send_shapes(const rfec_send_shapes* S, uint32_t groups, const rfec_send_group* group,
+                                        uint32_t n_rows, uint32_t n_fec, uint32_t stride, uint32_t capacity,
+                                        const uint8_t* shards, const rfec_hdr* hdr, const rfec_seg_stamp* seg_stamps,
+                                        const uint32_t* seg_order, uint8_t* seg_dgram, uint16_t* seg_dlen,
+                                        const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
+                                        uint8_t* fec_dgram, uint16_t* fec_dlen, uint32_t dstride, void* stream);
 /* rfec_wire_regroup (rfec_wire_regroup.c, kernels in rfec_regroup.hip): the call's four launches on `stream`.  The
  * caller has checked the arguments (groups in [1, 65535], k <= RFEC_MAX_K, n < 2^31, stride a multiple of 16 up to
  * 2,048, capacity <= stride, the pointers); hipErrorInvalidValue otherwise. */

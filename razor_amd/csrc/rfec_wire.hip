@@ -2231,6 +2231,208 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES)))
 }
 
 // ---------------------------------------------------------------------------
+// k_encode_send_q over a window whose groups have different shapes
+// (rfec_wire_encode_send_shapes): group G of the call is a descriptor -- its
+// first member row, its first SIM_FEC index and its plan's index -- and the
+// plans travel compacted in the argument block (rfec_send_shapes).
+//
+// Unit of work: a wave on four consecutive descriptors, a quarter-wave each.
+// The wave runs k_encode_send_q's line and orphan loops once per distinct shape
+// among its four (ballot, readlane): the plan walk stays on the scalar unit,
+// and a quarter whose group has another shape, is skipped or lies past the
+// call's end runs with its loads at kOut (no memory access) and its stores off,
+// as k_encode_send_q's tail quad does.  Four descriptors of one shape are one
+// pass with that kernel's loops.  row_g and the SIM_FEC index come from the
+// descriptor (one b128 load per quarter) where that kernel derives them from G.
+//
+// Per block, behind the CRC tables: every plan's lines (one dword each, shape
+// after shape), a dword per shape (k | n_lines << 8 | its first line's index
+// << 16) and every shape's own[] (256 bytes, built here from the lines: the
+// first line that holds the member, as rfec_launch_wire_encode_send's).
+//
+//
+// Resources from the build (gfx950, -O3): NR = 5: 128 VGPRs, no scratch, 48
+// SGPRs spilled to VGPR lanes, 4 waves per SIMD; NR = 2: 90 VGPRs, no scratch,
+// 33 SGPRs spilled; 118,912 bytes of LDS per block either way (one block per
+// CU, as k_encode_send_q's 109,056).  The descriptor's three dwords stay in
+// VGPRs across the passes; a pass's header lanes take their quarter's row0 by
+// ds_bpermute inside the pass, so it is not live beside the member windows.
+// ---------------------------------------------------------------------------
+constexpr int kShapesLdsDwords =
+    kQTabDwords + RFEC_SEND_MAX_LINES + RFEC_SEND_MAX_SHAPES + RFEC_SEND_MAX_SHAPES * 64 + kWavesPerBlock * 9 * kWave;
+static_assert(kShapesLdsDwords * 4 <= 160 * 1024, "k_encode_send_shapes_q's LDS: one block per CU within 160 KiB");
+static_assert(sizeof(rfec_send_group) == 16, "a descriptor is one b128 load");
+static_assert(sizeof(rfec_send_shapes) + 14 * 8 + 8 * 4 <= 4096, "k_encode_send_shapes_q's argument block");
+static_assert(RFEC_MAX_K_ENCODE <= 255 && RFEC_MAX_LINES <= 255 && RFEC_SEND_MAX_LINES <= 65535,
+              "a shape's dword: k | n_lines << 8 | first line << 16");
+
+template <int WAVES, int NR>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES))) void k_encode_send_shapes_q(
+    const rfec_send_group* __restrict__ group, const uint8_t* __restrict__ shards, const rfec_hdr* __restrict__ hdr,
+    const rfec_seg_stamp* __restrict__ sstamps, const uint32_t* __restrict__ sorder, uint8_t* __restrict__ sdgram,
+    uint16_t* __restrict__ sdlen, const rfec_fec_stamp* __restrict__ fstamps, const uint32_t* __restrict__ forder,
+    uint8_t* __restrict__ fdgram, uint16_t* __restrict__ fdlen, uint32_t groups, uint32_t n_rows, uint32_t n_fec,
+    uint32_t stride, uint32_t capacity, uint32_t dstride, rfec_send_shapes S)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t T[kShapesLdsDwords];
+    uint32_t* PL = T + kQTabDwords;             // the plans' lines
+    uint32_t* SH = PL + RFEC_SEND_MAX_LINES;    // the shapes' dwords
+    uint32_t* OW = SH + RFEC_SEND_MAX_SHAPES;   // the shapes' own[]: byte i of shape p at 256 p + i
+    uint32_t* HB = OW + RFEC_SEND_MAX_SHAPES * 64 + (threadIdx.x >> 6) * (9 * kWave);
+    const uint32_t lane = threadIdx.x & (kWave - 1), g = lane >> 4, s = lane & 15u;
+    const uint32_t nunits = (groups + 3u) / 4u;
+    const uint32_t nw = gridDim.x * kWavesPerBlock;
+    const uint32_t CD = (capacity + 15u) / 16u;
+    const uint32_t n_plans = S.n_plans;
+    const __amdgpu_buffer_rsrc_t rgd = rsrc64(group, (uint64_t)groups * sizeof(rfec_send_group));
+    const __amdgpu_buffer_rsrc_t rin = rsrc64(shards, (uint64_t)n_rows * stride);
+    const __amdgpu_buffer_rsrc_t rhd = rsrc64(hdr, (uint64_t)n_rows * sizeof(rfec_hdr));
+    const __amdgpu_buffer_rsrc_t rst = rsrc64(fstamps, (uint64_t)n_fec * sizeof(rfec_fec_stamp));
+    const __amdgpu_buffer_rsrc_t rso = rsrc64(sdgram, (uint64_t)n_rows * dstride);
+    const __amdgpu_buffer_rsrc_t rfo = rsrc64(fdgram, (uint64_t)n_fec * dstride);
+    constexpr uint32_t kOut = 0xFFFFFFF0u;
+    if (threadIdx.x < RFEC_SEND_MAX_LINES)
+        PL[threadIdx.x] = S.line[threadIdx.x];
+    else if (threadIdx.x < RFEC_SEND_MAX_LINES + RFEC_SEND_MAX_SHAPES)
+        SH[threadIdx.x - RFEC_SEND_MAX_LINES] = S.shape[threadIdx.x - RFEC_SEND_MAX_LINES];
+    // own[]: member i of shape p is framed on the first line that holds it, 0xFF: on none
+    for (uint32_t x = threadIdx.x; x < n_plans * 256u; x += kBlock) {
+        const uint32_t sd = S.shape[x >> 8], i = x & 255u;
+        const uint32_t n = (sd >> 8) & 0xffu, l0 = sd >> 16;
+        uint32_t o = 0xFFu;
+        if (i < (sd & 0xffu))
+            for (uint32_t l = 0; l < n; ++l) {
+                const uint32_t ln = S.line[l0 + l];
+                const uint32_t first = ln & 0xffu, step = (ln >> 8) & 0xffu, cnt = (ln >> 16) & 0xffu;
+                const uint32_t d = i - first, q = step ? d / step : 0u;
+                if (i >= first && q * step == d && q < cnt) {
+                    o = l;
+                    break;
+                }
+            }
+        reinterpret_cast<uint8_t*>(OW)[x] = (uint8_t)o;
+    }
+    fill_tables(T);
+    __syncthreads();
+    // one member's windows and, for lanes 6-11, its header dword (lane 11: the size), as k_encode_send_q's
+    auto load_member = [&](uint32_t row, bool on, v4u (&X)[NR], uint32_t& hv) {
+        const uint32_t pbase = row * stride;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const uint32_t c = 16u * k + s;
+            X[k] = __builtin_bit_cast(
+                v4u, __builtin_amdgcn_raw_buffer_load_b128(rin, on && c >= 2 && c - 2u < CD ? pbase + 16u * (c - 2u) : kOut,
+                                                           0, kAuxNT));
+        }
+        const uint32_t f = s - 6u;
+        const uint32_t v =
+            __builtin_amdgcn_raw_buffer_load_b32(rhd, on && f < 6u ? 20u * row + 4u * min(f, 4u) : kOut, 0, kAuxNT);
+        hv = s == 11 ? v >> 16 : v;
+    };
+    for (uint32_t u = wave_id(); u < nunits; u += nw) {
+        // the quarter's descriptor; a skipped group (razor_fec.h) or one past the call's end takes no pass
+        const uint32_t G = 4u * u + g;
+        const v4u D = __builtin_bit_cast(
+            v4u, __builtin_amdgcn_raw_buffer_load_b128(rgd, G < groups ? 16u * G : kOut, 0, 0));
+        const uint32_t sdq = SH[min(D[2], (uint32_t)RFEC_SEND_MAX_SHAPES - 1u)];
+        const bool live = G < groups && D[2] < n_plans && D[0] <= n_rows && (sdq & 0xffu) <= n_rows - D[0] &&
+                          D[1] <= n_fec && ((sdq >> 8) & 0xffu) <= n_fec - D[1];
+        const uint32_t shq = live ? D[2] : 0xFFFFFFFFu;
+        uint64_t todo = __builtin_amdgcn_ballot_w64(live);
+        while (todo) { // one pass per distinct shape of the four
+            const uint32_t cur = (uint32_t)__builtin_amdgcn_readlane((int)shq, __builtin_ctzll(todo));
+            const bool act = shq == cur;
+            todo &= ~__builtin_amdgcn_ballot_w64(act);
+            const uint32_t sd = (uint32_t)__builtin_amdgcn_readfirstlane((int)SH[cur]);
+            const uint32_t K = sd & 0xffu, n = (sd >> 8) & 0xffu;
+            const uint32_t* PLs = PL + (sd >> 16);
+            const uint32_t* OWs = OW + 64u * cur;
+            const uint32_t row_g = act ? D[0] : 0u, fec_g = act ? D[1] : 0u;
+            // SIM_SEG headers, 16 members of a line (or one orphan) at a time: lane 4 t + gg holds the header of
+            // quarter gg's member first + (j0 + t) step
+            auto pass = [&](uint32_t first, uint32_t step, uint32_t j0, uint32_t cnt) {
+                const uint32_t rp = bperm(act ? D[0] : 0xFFFFFFFFu, 16u * (lane & 3u)), jj = j0 + (lane >> 2);
+                const bool a = rp != 0xFFFFFFFFu && jj < cnt; // (a live group's row0 is at most n_rows - 1)
+                const SegHdrQ B = seg_header_q(hdr, sstamps, a ? rp + first + jj * step : 0u, a, capacity);
+                wave_lds_sync(); // the batch before this one has been read
+#pragma unroll
+                for (int f = 0; f < 8; ++f)
+                    HB[f * kWave + lane] = B.h[f];
+                HB[8 * kWave + lane] = B.m;
+                wave_lds_sync();
+            };
+            auto frame_seg = [&](const v4u (&W)[NR], uint32_t bt, uint32_t i) {
+                const uint32_t src = 4u * bt + g, d = row_g + i;
+                const uint32_t o = sorder ? sorder[d] : d;
+                frame_seg_store_a(T, W, HB, src, act, o, s, rso, sdlen, dstride, n_rows);
+            };
+            auto owner = [&](uint32_t i) {
+                return (uint32_t)__builtin_amdgcn_readfirstlane((int)OWs[i >> 2]) >> (8u * (i & 3u)) & 0xffu;
+            };
+            for (uint32_t l = 0; l < n; ++l) {
+                const uint32_t ln = (uint32_t)__builtin_amdgcn_readfirstlane((int)PLs[l]);
+                const uint32_t first = ln & 0xffu, step = (ln >> 8) & 0xffu, cnt = (ln >> 16) & 0xffu;
+                const uint32_t fd = fec_g + l;
+                uint32_t fv =
+                    __builtin_amdgcn_raw_buffer_load_b32(rst, act && s < 6 ? 24u * fd + 4u * s : kOut, 0, kAuxNT);
+                v4u A[NR];
+#pragma unroll
+                for (int k = 0; k < NR; ++k)
+                    A[k] = v4u{0u, 0u, 0u, 0u};
+                uint32_t j0 = 0xFFFFFFFFu; // the header batch holds members j0 .. j0 + 15 of this line
+                for (uint32_t j = 0; j < cnt; ++j) {
+                    const uint32_t i = first + j * step;
+                    v4u W[NR];
+                    uint32_t hv;
+                    load_member(row_g + i, act, W, hv);
+                    const bool own = owner(i) == l;
+                    if (own && (j & ~15u) != j0) {
+                        j0 = j & ~15u;
+                        pass(first, step, j0, cnt);
+                    }
+#pragma unroll
+                    for (int k = 0; k < NR; ++k)
+                        A[k] ^= W[k];
+                    fv = s == 11 ? max(fv, hv) : fv ^ hv;
+                    if (own)
+                        frame_seg(W, j & 15u, i);
+                }
+                // the line's SIM_FEC: the accumulator one lane up; lane 2 keeps payload dword 0 for chunk 2's end
+                v4u R[NR];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    uint32_t r[NR];
+#pragma unroll
+                    for (int k = 0; k < NR; ++k)
+                        r[k] = row_ror1(A[k][j]);
+#pragma unroll
+                    for (int k = 0; k < NR; ++k)
+                        R[k][j] = s == 0 ? (k ? r[k ? k - 1 : 0] : 0u) : r[k];
+                }
+                R[0][0] = s == 2 ? A[0][0] : R[0][0];
+                const uint32_t o = forder ? forder[fd] : fd;
+                uint32_t F[13];
+#pragma unroll
+                for (int i = 0; i < 13; ++i)
+                    F[i] = bperm(fv, 16u * g + i);
+                const bool valid = cnt > 1 && F[11] <= capacity;
+                frame_fec_store_q(T, R, F, valid, act && o < n_fec, o, s, rfo, fdlen, dstride);
+            }
+            // members that no line holds
+            for (uint32_t i = 0; i < K; ++i) {
+                if (owner(i) != 0xFFu)
+                    continue;
+                v4u W[NR];
+                uint32_t hv;
+                load_member(row_g + i, act, W, hv);
+                pass(i, 0u, 0u, 1u);
+                frame_seg(W, 0u, i);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Quarter-wave parse (slots of at most 1,280 bytes, or datagrams that fit
 // 1,280 bytes; payload slots of at most 1,280 bytes): the framing's layout
 // run backwards.  A wave parses four consecutive datagrams, 16 lanes each;
@@ -2567,6 +2769,41 @@ int rfec_launch_wire_encode_send(const rfec_kplan* P, uint32_t groups, uint32_t 
                     dim3(grid_for<10>((const void*)k_encode_send_q<kSendWaves, kQRows>, units)), dim3(kBlock), 0, sm,
                     shards, hdr, seg_stamps, seg_order, seg_dgram, seg_dlen, seg_rows_out, fec_stamps, fec_order,
                     fec_dgram, fec_dlen, fec_rows_out, groups, stride, capacity, dstride, *P, O);
+    return (int)hipGetLastError();
+}
+
+// The one launch of rfec_wire_encode_send_shapes (rfec_wire_fused.c, which has checked the plans and compacted
+// them into S): `groups` descriptors over n_rows member rows and n_fec SIM_FEC slots.
+int rfec_launch_wire_encode_send_shapes(const rfec_send_shapes* S, uint32_t groups, const rfec_send_group* group,
+                                        uint32_t n_rows, uint32_t n_fec, uint32_t stride, uint32_t capacity,
+                                        const uint8_t* shards, const rfec_hdr* hdr, const rfec_seg_stamp* seg_stamps,
+                                        const uint32_t* seg_order, uint8_t* seg_dgram, uint16_t* seg_dlen,
+                                        const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
+                                        uint8_t* fec_dgram, uint16_t* fec_dlen, uint32_t dstride, void* stream)
+{
+    hipStream_t sm = reinterpret_cast<hipStream_t>(stream);
+    if (S->n_plans < 1 || S->n_plans > RFEC_SEND_MAX_SHAPES || dstride > kQWindow || dstride % 16 || stride % 16 ||
+        ((uint64_t)n_rows + 4) * stride + kQWindow >= 0xFFFFFFF0ull ||
+        (uint64_t)n_rows * sizeof(rfec_hdr) >= 0xFFFFFFF0ull || (uint64_t)n_rows * dstride >= 0xFFFFFFF0ull ||
+        (uint64_t)n_fec * dstride >= 0xFFFFFFF0ull || (uint64_t)n_fec * sizeof(rfec_fec_stamp) >= 0xFFFFFFF0ull ||
+        (uint64_t)groups * sizeof(rfec_send_group) >= 0xFFFFFFF0ull)
+        return (int)hipErrorInvalidValue;
+    for (uint32_t p = 0; p < S->n_plans; ++p) { // every shape's lines inside the table
+        const uint32_t sd = S->shape[p];
+        if ((sd & 0xffu) < 1 || (sd >> 16) + ((sd >> 8) & 0xffu) > RFEC_SEND_MAX_LINES)
+            return (int)hipErrorInvalidValue;
+    }
+    const uint32_t units = (groups + 3u) / 4u;
+    if (dstride <= 512u) // two rows of 16 chunks hold the slot
+        RFEC_LAUNCH((k_encode_send_shapes_q<kSendWaves, 2>),
+                    dim3(grid_for<13>((const void*)k_encode_send_shapes_q<kSendWaves, 2>, units)), dim3(kBlock), 0, sm,
+                    group, shards, hdr, seg_stamps, seg_order, seg_dgram, seg_dlen, fec_stamps, fec_order, fec_dgram,
+                    fec_dlen, groups, n_rows, n_fec, stride, capacity, dstride, *S);
+    else
+        RFEC_LAUNCH((k_encode_send_shapes_q<kSendWaves, kQRows>),
+                    dim3(grid_for<12>((const void*)k_encode_send_shapes_q<kSendWaves, kQRows>, units)), dim3(kBlock), 0,
+                    sm, group, shards, hdr, seg_stamps, seg_order, seg_dgram, seg_dlen, fec_stamps, fec_order,
+                    fec_dgram, fec_dlen, groups, n_rows, n_fec, stride, capacity, dstride, *S);
     return (int)hipGetLastError();
 }
 

@@ -5,11 +5,13 @@
  * the launches through rfec_launch_wire_encode_fec, split over groups so that
  * every launch keeps 32-bit buffer offsets.  rfec_wire_encode_send: the same
  * for the batch's SIM_SEG and SIM_FEC datagrams in one kernel
- * (k_encode_send_q).
+ * (k_encode_send_q); rfec_wire_encode_send_shapes: that kernel's form for a
+ * window of several shapes (k_encode_send_shapes_q), one launch.
  *
  * Not one of build.py's HOST_SRC: the CPU builds of the host layer link
  * against a stub of the HIP runtime, which has no launch shims.
  */
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "razor_fec.h"
@@ -148,4 +150,91 @@ int rfec_wire_encode_send(const rfec_plan* plan, uint32_t groups, uint32_t strid
             return set_err(RFEC_EDEVICE, "wire_encode_send launch", e);
     }
     return RFEC_OK;
+}
+
+static int send_shapes_err(const char* what, const char* tail)
+{
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s%s", what, tail);
+    return set_err(RFEC_EINVAL, msg, 0);
+}
+
+/* rfec_wire_encode_send over a window of several shapes (razor_fec.h): the checks, the plans compacted into the
+ * kernel's argument block, one launch. */
+int rfec_wire_encode_send_shapes(const rfec_plan* plans, uint32_t n_plans, uint32_t groups,
+                                 const rfec_send_group* group, uint32_t n_rows, uint32_t n_fec, uint32_t stride,
+                                 uint32_t capacity, const uint8_t* shards, const rfec_hdr* hdr,
+                                 const rfec_seg_stamp* seg_stamps, const uint32_t* seg_order, uint8_t* seg_dgram,
+                                 uint16_t* seg_dlen, const rfec_fec_stamp* fec_stamps, const uint32_t* fec_order,
+                                 uint8_t* fec_dgram, uint16_t* fec_dlen, uint32_t dstride, void* stream)
+{
+    static const char split[] = " must stay below 0xFFFFFFF0 (32-bit buffer offsets): split the window";
+    if (!plans)
+        return set_err(RFEC_EINVAL, "plans is NULL", 0);
+    if (n_plans < 1 || n_plans > RFEC_SEND_MAX_SHAPES)
+        return set_err(RFEC_EINVAL, "n_plans must be in [1, RFEC_SEND_MAX_SHAPES]", 0);
+    rfec_send_shapes S;
+    uint32_t lines = 0;
+    S.n_plans = n_plans;
+    for (uint32_t p = 0; p < RFEC_SEND_MAX_SHAPES; ++p)
+        S.shape[p] = 0;
+    for (uint32_t p = 0; p < n_plans; ++p) {
+        const int rc = check_plan(plans + p, RFEC_MAX_K_ENCODE);
+        if (rc)
+            return rc;
+        const uint32_t n = plans[p].n_lines;
+        if (lines + n > RFEC_SEND_MAX_LINES)
+            return set_err(RFEC_EINVAL, "plans: the sum of n_lines must be <= RFEC_SEND_MAX_LINES", 0);
+        S.shape[p] = (uint32_t)plans[p].k | n << 8 | lines << 16;
+        for (uint32_t l = 0; l < n; ++l) {
+            const rfec_line* ln = &plans[p].line[l];
+            S.line[lines + l] = (uint32_t)ln->first | (uint32_t)ln->stride << 8 | (uint32_t)ln->count << 16;
+        }
+        lines += n;
+    }
+    for (uint32_t l = lines; l < RFEC_SEND_MAX_LINES; ++l)
+        S.line[l] = 0;
+    /* the SIM_FEC overhead covers the SIM_SEG's 36 */
+    const int rc = check_wire(n_rows > n_fec ? n_rows : n_fec, stride, capacity, dstride, RFEC_WIRE_FEC_OVERHEAD);
+    if (rc)
+        return rc;
+    if (dstride > WEF_MAX_DSTRIDE)
+        return set_err(RFEC_EINVAL,
+                       "rfec_wire_encode_send_shapes takes dstride <= 1280: use rfec_wire_frame_seg + "
+                       "rfec_wire_encode_fec per shape",
+                       0);
+    if (((uint64_t)n_rows + 4) * stride + WEF_MAX_DSTRIDE >= WEF_OFFSETS)
+        return send_shapes_err("(n_rows + 4) * stride + 1280", split);
+    if ((uint64_t)n_rows * sizeof(rfec_hdr) >= WEF_OFFSETS)
+        return send_shapes_err("n_rows * 20", split);
+    if ((uint64_t)n_rows * dstride >= WEF_OFFSETS)
+        return send_shapes_err("n_rows * dstride", split);
+    if ((uint64_t)n_fec * sizeof(rfec_fec_stamp) >= WEF_OFFSETS)
+        return send_shapes_err("n_fec * 24", split);
+    if ((uint64_t)n_fec * dstride >= WEF_OFFSETS)
+        return send_shapes_err("n_fec * dstride", split);
+    if ((uint64_t)groups * sizeof(rfec_send_group) >= WEF_OFFSETS)
+        return send_shapes_err("groups * 16", split);
+    if (groups == 0)
+        return RFEC_OK;
+    if (!group)
+        return set_err(RFEC_EINVAL, "group is NULL", 0);
+    if (!shards || !hdr || !seg_stamps || !seg_dgram || !seg_dlen)
+        return set_err(RFEC_EINVAL, "NULL buffer (shards, hdr, seg_stamps, seg_dgram, seg_dlen)", 0);
+    if (n_fec && (!fec_stamps || !fec_dgram || !fec_dlen))
+        return set_err(RFEC_EINVAL, "NULL buffer (fec_stamps, fec_dgram, fec_dlen)", 0);
+    if (misaligned(shards, 16) || misaligned(seg_dgram, 16) || (n_fec && misaligned(fec_dgram, 16)))
+        return set_err(RFEC_EINVAL, "shards, seg_dgram and fec_dgram must be 16-byte aligned", 0);
+    if (misaligned(group, 4) || misaligned(hdr, 4) || misaligned(seg_stamps, 4) || misaligned(seg_order, 4) ||
+        (n_fec && (misaligned(fec_stamps, 4) || misaligned(fec_order, 4))))
+        return set_err(RFEC_EINVAL, "group, hdr, seg_stamps, seg_order, fec_stamps and fec_order must be 4-byte aligned",
+                       0);
+    if (misaligned(seg_dlen, 2) || (n_fec && misaligned(fec_dlen, 2)))
+        return set_err(RFEC_EINVAL, "seg_dlen and fec_dlen must be 2-byte aligned", 0);
+    if (n_fec == 0)
+        fec_order = NULL;
+    const int e = rfec_launch_wire_encode_send_shapes(&S, groups, group, n_rows, n_fec, stride, capacity, shards, hdr,
+                                                      seg_stamps, seg_order, seg_dgram, seg_dlen, fec_stamps, fec_order,
+                                                      fec_dgram, fec_dlen, dstride, stream);
+    return e ? set_err(RFEC_EDEVICE, "wire_encode_send_shapes launch", e) : RFEC_OK;
 }

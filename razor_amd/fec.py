@@ -161,6 +161,19 @@ class rfec_regroup_section(C.Structure):
 assert C.sizeof(rfec_regroup_section) == 72
 
 
+RFEC_SEND_MAX_SHAPES = 32
+RFEC_SEND_MAX_LINES = 512  # the sum of n_lines over one call's plans
+
+
+class rfec_send_group(C.Structure):
+    """One group of rfec_wire_encode_send_shapes's window (a device array of these)."""
+    _fields_ = [("row0", C.c_uint32), ("line0", C.c_uint32), ("shape", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SEND_GROUP_DTYPE = np.dtype([("row0", "<u4"), ("line0", "<u4"), ("shape", "<u4"), ("reserved", "<u4")])
+assert C.sizeof(rfec_send_group) == 16 and SEND_GROUP_DTYPE.itemsize == 16
+
+
 class rfec_host_timing(C.Structure):
     _fields_ = [("gather_us", C.c_double), ("h2d_us", C.c_double), ("kernel_us", C.c_double),
                 ("d2h_us", C.c_double), ("scatter_us", C.c_double), ("total_us", C.c_double),
@@ -249,6 +262,9 @@ _SIGS = {
                                        C.c_uint32, _P, _P, _P]),
     "rfec_wire_encode_send": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P,
                                         _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
+    "rfec_wire_encode_send_shapes": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, _P, C.c_uint32,
+                                               C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, C.c_uint32, _P]),
     "rfec_wire_parse": (C.c_int, [C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "rfec_wire_regroup": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint16, C.c_uint32, _P, _P, C.c_uint32,
                                     C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -504,6 +520,18 @@ class Native:
                                                    seg_stamps, seg_order, seg_dgram, seg_dlen, fec_stamps, fec_order,
                                                    fec_dgram, fec_dlen, dstride, stream),
                     "rfec_wire_encode_send")
+
+    def wire_encode_send_shapes(self, plans, groups, group, n_rows, n_fec, stride, capacity, shards, hdr, seg_stamps,
+                                seg_dgram, seg_dlen, fec_stamps, fec_dgram, fec_dlen, dstride, stream=None,
+                                seg_order=None, fec_order=None):
+        """rfec_wire_encode_send_shapes: wire_encode_send over a window of several shapes in one launch.  plans:
+        a sequence of plans; group: the device array of `groups` rfec_send_group (SEND_GROUP_DTYPE) descriptors
+        over the window's n_rows member rows and n_fec SIM_FEC slots."""
+        pa = (rfec_plan * max(len(plans), 1))(*(as_plan(p) for p in plans))
+        self._check(self.lib.rfec_wire_encode_send_shapes(pa, len(plans), groups, group, n_rows, n_fec, stride,
+                                                          capacity, shards, hdr, seg_stamps, seg_order, seg_dgram,
+                                                          seg_dlen, fec_stamps, fec_order, fec_dgram, fec_dlen, dstride,
+                                                          stream), "rfec_wire_encode_send_shapes")
 
     def wire_parse(self, n, dstride, dgram, dlen, stride, capacity, recs, payload, stream=None):
         self._check(self.lib.rfec_wire_parse(n, dstride, dgram, dlen, stride, capacity, recs, payload, stream),
