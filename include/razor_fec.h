@@ -401,7 +401,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_shapes_out) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -933,6 +933,68 @@ int rfec_recover_indexed_matrix_out(const rfec_plan* plan, uint32_t groups, uint
                                     const rfec_hdr* meta, const uint16_t* fec_size, const uint64_t* parity_present,
                                     uint64_t* recovered, uint32_t per_group,
                                     uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index, void* stream);
+
+/*
+ * The decode behind rfec_wire_regroup_shapes: the sections of a closed window
+ * of several shapes in one launch and without a workspace, so that the receive
+ * chain of such a window is parse -> one regroup -> one decode.  plans
+ * [n_plans] and sections [n_plans] are the host arrays given to
+ * rfec_wire_regroup_shapes; of section p the call reads hdr, present, meta,
+ * fec_size, parity_present and src_of (base_id and group_of are ignored).
+ * groups [n_plans] is a host array, groups[p] <= sections[p].cap the number of
+ * rows of section p to decode -- min(counts[p], cap) for a caller that read the
+ * counts back -- or NULL for sections[p].cap: the trailing empty rows then
+ * decode to nothing.
+ *
+ * Output rows are dense over the call: row c of section p is output row
+ * o = first[p] + c, first[p] the sum of groups[q] over q < p.  recovered is
+ * indexed by o; out_index, out_hdr and out_shards by (o, e) with one
+ * per_group = E for the whole call.
+ *
+ * Plans accepted for a section with groups[p] > 0: the sender's full row +
+ * column plans of k = 6..16 (rfec_packed_matrix_stride(plan, 1) != 0), and the
+ * row layouts rfec_recover_indexed_out runs in one launch (rows of <= 4
+ * segments, k <= 64).  Any other plan gets RFEC_EINVAL, rfec_last_error names
+ * its index: give that section groups[p] == 0 and decode it with
+ * rfec_recover_indexed_out (an I-frame's strip plan, say).  A section with
+ * groups[p] == 0 only has to hold a valid plan; its tables may be NULL.
+ *
+ * Results: for every p with groups[p] > 0, output rows [first[p], first[p] +
+ * groups[p]) hold byte for byte what rfec_recover_indexed_matrix_out (a full
+ * matrix) or rfec_recover_indexed_out (a row layout) writes into arrays of its
+ * own for (&plans[p], groups[p], stride, capacity, rows, n_rows, section p's
+ * tables, per_group): recovered, out_index, out_hdr, and out_shards over
+ * [0, 16 CD) of every slot whose out_index is not 0xFF.  Bytes [16 CD, stride)
+ * of every out slot are not written; the payload of a 0xFF slot is
+ * unspecified; every input is untouched.  The clamp of a row index to
+ * n_rows - 1, the 64-bit row addresses and n_rows == 0 (no row is read:
+ * recovered, out_hdr and out_index are still written) are those calls'.
+ * rfec_set_tuning does not reach this call.
+ *
+ * Checked before any runtime call (RFEC_EINVAL), in rfec_recover_indexed_out's
+ * order: n_plans in [1, RFEC_RECOVER_MAX_SHAPES], each plan and, with
+ * groups[p] > 0, its shape; stride a positive multiple of 16,
+ * capacity <= stride, per_group in [1, the least k of the sections with
+ * groups]; per section groups[p] <= cap, groups[p] * per_group * CD < 2^31 and
+ * the header lanes' bound of its own call (groups * 4, or groups x the least
+ * power of two >= n_lines, < 2^32); the launch's blocks (the sections' own
+ * grids, end to end) < 2^31 and its output rows < 2^32.  All groups[p] == 0
+ * touches nothing: every other pointer may be NULL.  Then NULL pointers (rows
+ * may be NULL when n_rows == 0) and alignment: 16 bytes rows and out_shards;
+ * 8 bytes present, parity_present and recovered; 4 bytes src_of, hdr, meta and
+ * out_hdr; 2 bytes fec_size.  The call allocates nothing, copies nothing from
+ * the host (the sections travel as kernel arguments), does not synchronise and
+ * makes exactly one launch on `stream`.
+ */
+#define RFEC_RECOVER_MAX_SHAPES RFEC_REGROUP_MAX_SHAPES
+int rfec_recover_indexed_shapes_out(const rfec_plan* plans, uint32_t n_plans,
+                                    const rfec_regroup_section* sections,
+                                    const uint32_t* groups, /* host [n_plans], or NULL: sections[p].cap */
+                                    uint32_t stride, uint32_t capacity,
+                                    const uint8_t* rows, uint32_t n_rows,
+                                    uint64_t* recovered, uint32_t per_group,
+                                    uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index,
+                                    void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Sender staging: sim_sender_put (sim_sender.c:306-377) with sim_split_frame */

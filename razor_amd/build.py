@@ -39,19 +39,21 @@ HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused"
 # drop-in; rfec_packed_matrix.c (the packed matrix records' entry points) and rfec_wire_fused.c (the fused encode +
 # SIM_FEC framing's), rfec_wire_regroup.c (parsed datagrams into the batch layout, its index-only form and the index-only form over
 # a window of several shapes) and
-# rfec_recover_indexed.c (the dense decode through a row map) and rfec_recover_indexed_matrix.c (its one-launch form
-# for the sender's matrix plans) call launch shims of their own,
+# rfec_recover_indexed.c (the dense decode through a row map), rfec_recover_indexed_matrix.c (its one-launch form
+# for the sender's matrix plans) and rfec_recover_indexed_shapes.c (its one-launch form for a window's sections of
+# several shapes) call launch shims of their own,
 # so they stay out of HOST_SRC: the CPU builds of the host layer compile exactly HOST_SRC against a stub of the runtime
 HOST_NOHIP_SRC = ["rfec_rx_sim.c", "rfec_rx_pool.c", "rfec_rx_plane.c"]  # no GPU runtime: built and tested alone
 HOST_SRC = ["rfec_host.c", "rfec_dropin.c", "rfec_hostmem.c", "rfec_sender.c", *HOST_NOHIP_SRC, "rfec_rx_dev.c",
             "rfec_rx_session.c"]
 C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packed_matrix.c",
                                           CSRC / "rfec_wire_fused.c", CSRC / "rfec_wire_regroup.c",
-                                          CSRC / "rfec_recover_indexed.c", CSRC / "rfec_recover_indexed_matrix.c"]
+                                          CSRC / "rfec_recover_indexed.c", CSRC / "rfec_recover_indexed_matrix.c",
+                                          CSRC / "rfec_recover_indexed_shapes.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h", CSRC / "rfec_device.h", CSRC / "rfec_families.h",
-           CSRC / "rfec_regroup_rules.h"]
+           CSRC / "rfec_row_blocks.h", CSRC / "rfec_regroup_rules.h"]
 # the receiver units' own headers: only the C host layer includes them
 HOST_HEADERS = HEADERS + [CSRC / f"rfec_rx_{u}.h" for u in ("map", "sim", "pool", "plane", "dev")]
 

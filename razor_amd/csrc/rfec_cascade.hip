@@ -1,7 +1,9 @@
 // rfec_cascade.hip -- the cascade and matrix decodes of the flex-FEC engine (gfx950), the packed matrix
-// records' packer and decode, the matrix decode through a slot map over a row pool, and their launchers;
+// records' packer and decode, the matrix decode through a slot map over a row pool, the decode of a window's
+// sections of several shapes through that map (matrix and row-layout sections in one launch), and their launchers;
 // rfec_kernels.hip picks the cascade decode (rfec_launch_recover[_out]), rfec_packed_matrix.c calls the packed
-// records' shims, rfec_recover_indexed_matrix.c the indexed matrix decode's.
+// records' shims, rfec_recover_indexed_matrix.c the indexed matrix decode's, rfec_recover_indexed_shapes.c the
+// sections'.
 //
 // One copy of each piece: the replay and the dense tail take the received rows as a row source (BatchRows: the
 // batch layout; PoolRows: a row pool through the slot map), the three matrix kernels share matrix_payload_block
@@ -9,7 +11,7 @@
 // dense-output arguments for the three launch paths.  Only the dependency closure over a schedule stands twice
 // (k_decode_cascade and cascade_dense_tail).  The batch kernels' code is sensitive to the form of such sharing,
 // not only to its content: DESIGN 7.13 lists the forms that changed it, and tools/kernel_compare.py is the check.
-#include "rfec_families.h"
+#include "rfec_row_blocks.h" // (the row sections of k_decode_shapes_indexed: rfec_fused.hip's bodies)
 
 namespace {
 
@@ -873,6 +875,141 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         matrix_payload_block<K, COL>(A, HS, PoolRows{rows, src_of, K, last, A.C}, pb);
 }
 
+// The sections of a window of several shapes (rfec_wire_regroup_shapes' dense tables, one section per shape) in
+// one launch (rfec_recover_indexed_shapes_out): every section gets the grid its own call would get --
+// k_decode_matrix_indexed's for a full matrix of k = 6..16, k_decode_rows_indexed<0, 4>'s for a row layout -- and
+// the grids lie end to end.  Each is a whole number of rounds of 8 blocks, so a block's index within its section
+// keeps its residue mod 8 and with it the XCD it has in the single call.  A block finds its section in the prefix
+// of first blocks (wave-uniform: the section's arguments come through scalar loads) and runs that section's body
+// on its relative index; the sections' outputs are the call's four arrays from the section's first output row on.
+//
+// The bodies are the single calls' own (cascade_check_block / matrix_payload_block, line_headers /
+// RFEC_ROWS_INDEXED_LANE), their CascArgs / PeelArgs built in registers from the section's arguments.  The checker's
+// serial peel and the header lanes index the plan's lines and masks at run time, and an argument block has no room
+// for an rfec_kmask per section: a header block builds the one of its section in LDS (a matrix's lines and masks
+// from MatLines, a row layout's from (k, col)) before it runs the body.  The payload lanes read none of it.
+constexpr uint32_t kShapeMatrix = 1u << 24;
+
+struct ShapeSec {
+    const uint32_t* src_of;
+    const uint32_t* hdr_dw;
+    const uint64_t* present;
+    const uint32_t* meta_dw;
+    const uint16_t* fsize;
+    const uint64_t* parity_present;
+    uint32_t groups, first_row; // rows decoded; the first of its output rows
+    uint32_t shape;             // k | col << 8 | log2 of the header lanes per group << 12 | n_lines << 16 | kShapeMatrix
+    uint32_t every;             // payload rounds per header round (Rounds8)
+};
+static_assert(sizeof(ShapeSec) == 64, "the argument block's budget per section");
+
+struct ShapesArgs {
+    ShapeSec sec[RFEC_RECOVER_MAX_SHAPES];                // the sections with groups, in order
+    uint32_t first_block[RFEC_RECOVER_MAX_SHAPES];        // of each, a multiple of 8
+    uint32_t n;
+    const v4u* rows;
+    uint32_t last, has_rows; // n_rows - 1 (0: none); n_rows != 0 (else no payload lanes)
+    uint64_t* recovered;
+    v4u* out_sh;
+    uint32_t* out_hdr_dw;
+    uint8_t* out_index;
+    uint32_t E, C, cd, capacity;
+    FastDiv divC, divQC;  // cd, E * cd
+    FastDiv divCol[3];    // a row layout's col = 2, 3, 4
+};
+static_assert(sizeof(ShapesArgs) <= 4096, "one argument block");
+
+template <int K, int COL>
+__device__ __forceinline__ void shapes_matrix_block(const CascArgs& A, rfec_kmask& sM, bool checker,
+                                                    uint32_t hb, uint32_t pb, const v4u* rows, uint32_t last,
+                                                    const uint32_t* __restrict__ src_of)
+{
+    using LL = MatLines<K, COL>;
+    if (checker) {
+        if (threadIdx.x == 0) {
+            sM.plan.k = K;
+            sM.plan.n_lines = LL::NL;
+        }
+        if (threadIdx.x < (uint32_t)LL::NL) { // (what the serial peel reads: KArgLines)
+            reinterpret_cast<uint32_t*>(sM.plan.line)[threadIdx.x] = LL{}.rec(threadIdx.x);
+            sM.mask[threadIdx.x][0] = LL{}.mask(threadIdx.x);
+            sM.mask[threadIdx.x][1] = 0;
+        }
+        __syncthreads();
+        cascade_check_block<uint32_t, false>(A, sM, LL{}, BatchHdrs{A, sM.plan}, hb);
+    } else {
+        matrix_payload_block<K, COL>(A, BatchHdrs{A, sM.plan}, PoolRows{rows, src_of, K, last, A.C}, pb);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_decode_shapes_indexed(ShapesArgs S)
+{
+    __shared__ rfec_kmask sM;
+    uint32_t p = 0;
+    for (uint32_t q = 1; q < S.n; ++q) // (uniform: scalar loads and compares)
+        p = blockIdx.x >= S.first_block[q] ? q : p;
+    const ShapeSec& T = S.sec[p];
+    const uint32_t rb = blockIdx.x - S.first_block[p];
+    const uint32_t G = T.groups, K = T.shape & 0xffu, lg = (T.shape >> 12) & 15u;
+    // the section's grid, as its own call lays it out (rounds_of_8): G << lg < 2^32 and total < 2^31, host-checked
+    const uint32_t total = S.has_rows ? G * S.E * S.cd : 0u, hl = G << lg;
+    const uint32_t n_hdr = (hl >> 8) + ((hl & 255u) != 0), npay8 = (((total + 255u) >> 8) + 7u) & ~7u;
+    uint32_t hb = 0, pb = 0;
+    const bool header = header_block_xcd_at(rb, (n_hdr + 7u) >> 3, T.every, npay8, &hb, &pb);
+    const size_t o = T.first_row;
+    if (T.shape & kShapeMatrix) {
+        CascArgs A = {}; // (no shards, no parity, no workspace: rfec_launch_recover_indexed_matrix's)
+        A.hdr_dw = const_cast<uint32_t*>(T.hdr_dw);
+        A.meta_dw = T.meta_dw, A.fsize = T.fsize, A.present = T.present, A.parity_present = T.parity_present;
+        A.recovered = S.recovered + 2 * o;
+        A.out_sh = S.out_sh + o * S.E * S.C;
+        A.out_hdr_dw = S.out_hdr_dw + o * S.E * 5;
+        A.out_index = S.out_index + o * S.E;
+        A.E = A.Q = S.E, A.groups = G, A.total = total, A.C = S.C, A.capacity = S.capacity;
+        A.divC = S.divC, A.divQC = S.divQC;
+#define RFEC_MS(KK, CC)                                                                                           \
+    case KK: shapes_matrix_block<KK, CC>(A, sM, header, hb, pb, S.rows, S.last, T.src_of); break;
+        switch (K) {
+            RFEC_MATRIX_SHAPES(RFEC_MS)
+        default: break;
+        }
+#undef RFEC_MS
+        return;
+    }
+    // a row layout: k and col at run time, the masks from (k, col)
+    const uint32_t col = (T.shape >> 8) & 15u, NL = (T.shape >> 16) & 0xffu;
+    PeelArgs B = {};
+    B.hdr = reinterpret_cast<rfec_hdr*>(const_cast<uint32_t*>(T.hdr_dw)); // dense output: hdr is only read
+    B.present = T.present;
+    B.meta = reinterpret_cast<const rfec_hdr*>(T.meta_dw);
+    B.fsize = T.fsize, B.parity_present = T.parity_present;
+    B.recovered = S.recovered + 2 * o;
+    B.groups = G, B.capacity = S.capacity, B.gpb = 1, B.nlp_log2 = lg;
+    B.out_hdr = reinterpret_cast<rfec_hdr*>(S.out_hdr_dw + o * S.E * 5);
+    B.out_index = S.out_index + o * S.E;
+    B.out_per_group = S.E;
+    if (header) {
+        if (hb >= n_hdr)
+            return;
+        if (threadIdx.x == 0) {
+            sM.plan.k = (uint16_t)K;
+            sM.plan.n_lines = (uint8_t)NL;
+        }
+        if (threadIdx.x < NL) { // row l: members l col .. of the k
+            const uint32_t first = threadIdx.x * col, cnt = min(col, K - first);
+            reinterpret_cast<uint32_t*>(sM.plan.line)[threadIdx.x] = first | 1u << 8 | cnt << 16;
+            sM.mask[threadIdx.x][0] = ((1ull << cnt) - 1ull) << first;
+            sM.mask[threadIdx.x][1] = 0;
+        }
+        __syncthreads();
+        [[clang::always_inline]] line_headers(B, sM, hb); // (a call would put B on the stack: scratch)
+        return;
+    }
+    const DenseOut D = {S.out_sh + o * S.E * S.C, S.E};
+    RFEC_ROWS_INDEXED_LANE(0, 4, S.rows, S.last, T.src_of, total, S.C, S.divC, S.divQC, B, D, K, col,
+                           S.divCol[col - 2u], pb)
+}
+
 // The batch layout -> packed matrix records (rfec_pack_erasures_matrix): one
 // lane per (group, 16-byte chunk of the record), so every byte of a record --
 // masks, slots, zeros and padding -- leaves in whole 16-byte stores (slots
@@ -1100,6 +1237,82 @@ int rfec_launch_recover_indexed_matrix(const rfec_kmask* M, uint32_t groups, uin
     default: break;
     }
 #undef RFEC_MI
+    return (int)hipGetLastError();
+}
+
+// A section's part of k_decode_shapes_indexed's grid: rfec_launch_recover_indexed_matrix's (the checker's lanes per
+// group) or launch_rows_indexed's (header lanes per (group, line)); with n_rows == 0 the header rounds alone.
+static bool shapes_section_grid(const rfec_kplan* P, uint32_t groups, uint32_t E, uint32_t cd, uint32_t n_rows,
+                                uint32_t* lg, Rounds8* g)
+{
+    const bool matrix = rfec_packed_matrix_col(P) != 0;
+    if (!matrix && !rfec_rows_indexed_col(P))
+        return false;
+    *lg = matrix ? rfec_ceil_log2(kCheckLanes) : rfec_header_lanes_log2(P->n_lines);
+    *g = rounds_of_8(blocks_for((uint64_t)groups << *lg), blocks_for(n_rows ? (uint64_t)groups * E * cd : 0));
+    return true;
+}
+
+uint32_t rfec_recover_shapes_blocks(const rfec_kplan* P, uint32_t groups, uint32_t per_group, uint32_t cd,
+                                    uint32_t n_rows)
+{
+    uint32_t lg;
+    Rounds8 g;
+    return shapes_section_grid(P, groups, per_group, cd, n_rows, &lg, &g) ? g.grid : 0u;
+}
+
+// rfec_recover_indexed_shapes_out (rfec_recover_indexed_shapes.c): one launch of k_decode_shapes_indexed over the
+// sections with groups, no workspace.
+int rfec_launch_recover_indexed_shapes(const rfec_kplan* plans, uint32_t n_plans, const rfec_regroup_section* sections,
+                                       const uint32_t* groups, uint32_t stride, uint32_t capacity, const uint8_t* rows,
+                                       uint32_t n_rows, uint64_t* recovered, const rfec_dense_out* out, void* stream)
+{
+    const uint32_t cd = capacity ? (capacity + 15) / 16 : 1, E = out ? out->per_group : 0;
+    if (!plans || !sections || !n_plans || n_plans > RFEC_RECOVER_MAX_SHAPES || !stride || stride % 16 ||
+        capacity > stride || !E)
+        return (int)hipErrorInvalidValue;
+    ShapesArgs S = {};
+    uint64_t blocks = 0, first_row = 0;
+    for (uint32_t p = 0; p < n_plans; ++p) {
+        const rfec_kplan* P = plans + p;
+        const uint32_t G = groups ? groups[p] : sections[p].cap;
+        if (!G)
+            continue;
+        uint32_t lg;
+        Rounds8 g;
+        if (!shapes_section_grid(P, G, E, cd, n_rows, &lg, &g) || E > P->k || (uint64_t)G * E * cd >= (1ull << 31) ||
+            ((uint64_t)G << lg) >= (1ull << 32))
+            return (int)hipErrorInvalidValue;
+        const rfec_regroup_section& s = sections[p];
+        const uint32_t mcol = (uint32_t)rfec_packed_matrix_col(P);
+        ShapeSec& T = S.sec[S.n];
+        T.src_of = s.src_of, T.hdr_dw = reinterpret_cast<const uint32_t*>(s.hdr), T.present = s.present;
+        T.meta_dw = reinterpret_cast<const uint32_t*>(s.meta), T.fsize = s.fec_size;
+        T.parity_present = s.parity_present;
+        T.groups = G, T.first_row = (uint32_t)first_row, T.every = g.every;
+        T.shape = P->k | (mcol ? mcol : (uint32_t)rfec_rows_indexed_col(P)) << 8 | lg << 12 |
+                  (uint32_t)P->n_lines << 16 | (mcol ? kShapeMatrix : 0u);
+        S.first_block[S.n++] = (uint32_t)blocks;
+        blocks += g.grid;
+        first_row += G;
+        if (blocks >= (1ull << 31) || first_row >= (1ull << 32))
+            return (int)hipErrorInvalidValue;
+    }
+    if (!S.n)
+        return (int)hipSuccess;
+    S.rows = reinterpret_cast<const v4u*>(rows);
+    S.last = n_rows ? n_rows - 1 : 0u, S.has_rows = n_rows != 0;
+    S.recovered = recovered;
+    S.out_sh = reinterpret_cast<v4u*>(out->shards);
+    S.out_hdr_dw = reinterpret_cast<uint32_t*>(out->hdr);
+    S.out_index = out->index;
+    S.E = E, S.C = stride / 16, S.cd = cd, S.capacity = capacity;
+    S.divC = make_fastdiv(cd), S.divQC = make_fastdiv(E * cd);
+    for (uint32_t c = 2; c <= 4; ++c)
+        S.divCol[c - 2] = make_fastdiv(c);
+    rfec_set_indexed_path(4u | S.n << 8);
+    RFEC_LAUNCH(k_decode_shapes_indexed, dim3((uint32_t)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+                S);
     return (int)hipGetLastError();
 }
 

@@ -104,6 +104,31 @@ __device__ __forceinline__ bool header_block_xcd(uint32_t n_hr, uint32_t every, 
     return false;
 }
 
+// header_block_xcd for a grid that starts at a multiple of 8 inside a larger one (k_decode_shapes_indexed: one
+// such grid per section): b is the block's index relative to the grid's first block, so b % 8 is still its XCD.
+__device__ __forceinline__ bool header_block_xcd_at(uint32_t b, uint32_t n_hr, uint32_t every, uint32_t npay8,
+                                                    uint32_t* hb, uint32_t* pb)
+{
+    const uint32_t R = b >> 3, x = b & 7u;
+    uint32_t pr;
+    if (!every) {
+        if (R < n_hr) {
+            *hb = x * n_hr + R;
+            return true;
+        }
+        pr = R - n_hr;
+    } else {
+        const uint32_t per = R / (every + 1);
+        if (per < n_hr && R == per * (every + 1)) {
+            *hb = x * n_hr + per;
+            return true;
+        }
+        pr = R - min(per + 1, n_hr);
+    }
+    *pb = xcd_block(pr * 8u + x, npay8);
+    return false;
+}
+
 // Header blocks of the fused decodes: every (every + 1)-th block until they
 // run out (every == 0: the first n_hdr of the grid), spread over the grid so
 // their latency-bound chains overlap the payload stream (cold: k = 32 / 256 B

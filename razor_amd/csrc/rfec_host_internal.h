@@ -3,7 +3,8 @@
  * translation units that use the HIP runtime (rfec_host.c, rfec_dropin.c,
  * rfec_hostmem.c, rfec_sender.c, rfec_rx_dev.c, rfec_rx_session.c,
  * rfec_packed_matrix.c, rfec_wire_fused.c, rfec_wire_regroup.c,
- * rfec_recover_indexed.c, rfec_recover_indexed_matrix.c; the
+ * rfec_recover_indexed.c, rfec_recover_indexed_matrix.c,
+ * rfec_recover_indexed_shapes.c; the
  * receiver's host-only units rfec_rx_sim.c, rfec_rx_pool.c, rfec_rx_plane.c
  * do without it).  Internal: hidden from the shared library's exports.
  */

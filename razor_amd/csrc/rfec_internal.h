@@ -215,11 +215,32 @@ int rfec_launch_recover_indexed_matrix(const rfec_kmask* M, uint32_t groups, uin
                                        const rfec_hdr* hdr, const uint64_t* present, const rfec_hdr* meta,
                                        const uint16_t* fsize, const uint64_t* parity_present, uint64_t* recovered,
                                        const rfec_dense_out* out, void* stream);
-/* Which kernels the calling thread's last rfec_launch_recover_indexed or rfec_launch_recover_indexed_matrix took
- * (host-side, thread-local, for tests; apart from rfec_last_path, whose kinds are a closed table): 0 none yet,
+/* The plans rfec_launch_recover_indexed runs in one launch of k_decode_rows_indexed: the row width of a row layout
+ * with rows of <= 4 segments and k <= 64, 0 for any other plan. */
+int rfec_rows_indexed_col(const rfec_kplan* P);
+/* rfec_recover_indexed_shapes_out (rfec_recover_indexed_shapes.c, kernel in rfec_cascade.hip): the sections of
+ * rfec_wire_regroup_shapes decoded in one launch of k_decode_shapes_indexed, section p's first groups[p] rows
+ * (groups NULL: sections[p].cap) as rfec_launch_recover_indexed_matrix (rfec_packed_matrix_col != 0) or as
+ * rfec_launch_recover_indexed's one launch (rfec_rows_indexed_col != 0) decodes them, into output rows
+ * first[p] + c of out and recovered, first[p] the sum of the groups before p.  The caller has checked n_plans in
+ * [1, RFEC_RECOVER_MAX_SHAPES], each plan, that every section with groups[p] > 0 has one of the two shapes and the
+ * two calls' bounds for it (out->per_group <= k among them), its pointers, and that the sections' blocks
+ * (rfec_recover_shapes_blocks) sum to less than 2^31; hipErrorInvalidValue otherwise.  All groups[p] == 0: no
+ * launch.  No flags: rfec_set_tuning does not reach this call. */
+int rfec_launch_recover_indexed_shapes(const rfec_kplan* plans, uint32_t n_plans, const rfec_regroup_section* sections,
+                                       const uint32_t* groups, uint32_t stride, uint32_t capacity, const uint8_t* rows,
+                                       uint32_t n_rows, uint64_t* recovered, const rfec_dense_out* out, void* stream);
+/* the blocks of one section's part of that launch's grid, a multiple of 8: the grid its own call would take (cd:
+ * 16-byte chunks of work per slot); 0 for a plan of neither shape */
+uint32_t rfec_recover_shapes_blocks(const rfec_kplan* P, uint32_t groups, uint32_t per_group, uint32_t cd,
+                                    uint32_t n_rows);
+/* Which kernels the calling thread's last rfec_launch_recover_indexed, rfec_launch_recover_indexed_matrix or
+ * rfec_launch_recover_indexed_shapes took (host-side, thread-local, for tests; apart from rfec_last_path, whose
+ * kinds are a closed table): 0 none yet,
  * 1 | K << 8 one launch of k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8
  * k_peel_lds + k_recover_indexed<MAXC, ...> (MAXC = 4, 8), 3 | K << 8 one launch of k_decode_matrix_indexed<K, col>
- * (K = 6..16; rfec_launch_recover_indexed_matrix only). */
+ * (K = 6..16; rfec_launch_recover_indexed_matrix only), 4 | n << 8 one launch of k_decode_shapes_indexed over n
+ * sections with groups (rfec_launch_recover_indexed_shapes only). */
 uint32_t rfec_indexed_last_path(void);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */

@@ -220,8 +220,8 @@ int rfec_launch_recover_indexed(const rfec_kmask* M, uint32_t groups, uint32_t s
     const v4u* pool = reinterpret_cast<const v4u*>(rows);
     const uint32_t last = n_rows ? n_rows - 1 : 0;
     const DenseOut DO = {reinterpret_cast<v4u*>(out->shards), E};
-    uint32_t col = 0;
-    if (n_rows && !(flags & RFEC_KFLAG_GENERIC) && is_row_layout(&P, &col) && col <= 4 && P.k <= 64) {
+    const uint32_t col = (uint32_t)rfec_rows_indexed_col(&P);
+    if (n_rows && !(flags & RFEC_KFLAG_GENERIC) && col) {
         // launch_fused_rows' grid: header lanes per (group, line), payload lanes per (group, out slot, chunk)
         B.gpb = 1;
         B.nlp_log2 = lg;
@@ -258,6 +258,12 @@ int rfec_launch_recover_out(const rfec_kmask* M, uint32_t groups, uint32_t strid
     // the fused decodes only read the shards and headers when the output is dense
     return launch_recover(M, groups, stride, capacity, const_cast<uint8_t*>(shards), const_cast<rfec_hdr*>(hdr),
                           present, parity, meta, fsize, parity_present, recovered, ws, stream, flags, out);
+}
+
+int rfec_rows_indexed_col(const rfec_kplan* P)
+{
+    uint32_t col = 0;
+    return is_row_layout(P, &col) && col <= 4 && P->k <= 64 ? (int)col : 0;
 }
 
 int rfec_packed_matrix_col(const rfec_kplan* P)

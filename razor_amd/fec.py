@@ -276,6 +276,9 @@ _SIGS = {
                                            _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "rfec_recover_indexed_matrix_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P,
                                                   C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
+    "rfec_recover_indexed_shapes_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
+                                                  C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_uint32, _P,
+                                                  C.c_uint32, _P, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "rfec_host_send_frames": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
@@ -588,6 +591,23 @@ class Native:
                                                              n_rows, src_of, hdr, present, meta, fec_size,
                                                              parity_present, recovered, per_group, out_shards, out_hdr,
                                                              out_index, stream), "rfec_recover_indexed_matrix_out")
+
+    def recover_indexed_shapes_out(self, plans, sections, groups, stride, capacity, rows, n_rows, recovered,
+                                   per_group, out_shards, out_hdr, out_index, stream=None):
+        """rfec_recover_indexed_shapes_out: the sections of wire_regroup_shapes (the same plans / sections lists)
+        decoded in one launch, the first groups[p] rows of section p (groups None: every section's cap) into
+        output rows sum(groups[:p]) + c of recovered / out_shards / out_hdr / out_index."""
+        if len(plans) != len(sections):
+            raise ValueError("one section per plan")
+        if groups is not None and len(groups) != len(plans):
+            raise ValueError("one group count per plan")
+        pa = (rfec_plan * max(len(plans), 1))(*(as_plan(p) for p in plans))
+        sa = (rfec_regroup_section * max(len(sections), 1))(
+            *(s if isinstance(s, rfec_regroup_section) else rfec_regroup_section(**s) for s in sections))
+        ga = None if groups is None else (C.c_uint32 * max(len(groups), 1))(*(int(g) for g in groups))
+        self._check(self.lib.rfec_recover_indexed_shapes_out(pa, len(plans), sa, ga, stride, capacity, rows, n_rows,
+                                                             recovered, per_group, out_shards, out_hdr, out_index,
+                                                             stream), "rfec_recover_indexed_shapes_out")
 
     # -- sender staging (host memory) -------------------------------------------
     def sender_init(self):
