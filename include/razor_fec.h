@@ -401,7 +401,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_shapes_out) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_shapes_out, rfec_recover_deliver) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -996,6 +996,95 @@ int rfec_recover_indexed_shapes_out(const rfec_plan* plans, uint32_t n_plans,
                                     uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index,
                                     void* stream);
 
+/* One delivered segment, as every call that hands recovered segments back
+ * writes it (rfec_recover_deliver below; rfec_rx_recover, the rx session). */
+typedef struct {
+    rfec_hdr hdr;     /* recovered header (flex_fec_xor.c:64-85) */
+    uint16_t fec_id;  /* out_seg->fec_id = fec->fec_id (:101) */
+    uint16_t reserved;
+} rfec_rx_seg; /* 24 bytes */
+
+/*
+ * The last stage of a closed window's receive chain: what
+ * rfec_recover_indexed_shapes_out wrote -- dense over the sections, per_group
+ * out slots a row, a hole wherever out_index is 0xFF, the rows in section order
+ * -- as the list a receiver uses: one rfec_rx_seg and one payload row per
+ * recovered segment, in window order.  plans, sections, groups and per_group
+ * are exactly the arguments given to rfec_recover_indexed_shapes_out (of
+ * section p the call reads cap and group_of); window_groups = G, fec_id0,
+ * shape_of and rank_of are those of rfec_wire_regroup_shapes.  plans, sections
+ * and groups are host arrays, everything else is a device pointer.
+ *
+ * The rule, independent of how the device schedules the work:
+ *  1. Output rows.  first[p] is the sum of groups[q] over q < p, groups[p] =
+ *     sections[p].cap when groups is NULL; R = first[n_plans].  This is the
+ *     decode's own numbering.
+ *  2. Decoded groups.  Window group g in [0, G) is decoded when p = shape_of[g]
+ *     < n_plans and c = rank_of[g] < groups[p]; its output row is o(g) =
+ *     first[p] + c.  Any other group delivers nothing: RFEC_REGROUP_NONE, shape
+ *     0xFF, a rank past the rows decoded, a section left to the generic call
+ *     (groups[p] == 0).
+ *  3. Counts.  n_g is the number of e < per_group with out_index[o(g) per_group
+ *     + e] != 0xFF; 0 for a group that is not decoded.
+ *  4. Prefix.  first_of[g] is the sum of n_g' over g' < g, first_of[G] the
+ *     total T, and *n_out = T.  Neither is clamped to max_out, as counts is not
+ *     clamped to cap: a caller sees overflow as *n_out > max_out.
+ *  5. Order.  Window order and, within a group, out-slot order (ascending
+ *     segment index): out slot e of group g is entry j = first_of[g] + the
+ *     number of e' < e with out_index[o(g) per_group + e'] != 0xFF.
+ *  6. Entries.  For j < max_out: seg[j].hdr is out_hdr[o per_group + e],
+ *     seg[j].fec_id = ((fec_id0 - 1 + g) % 65535) + 1 (the regroup's succession
+ *     65535 -> 1), seg[j].reserved = 0, and row j of seg_payload over [0, 16 CD)
+ *     is the out slot's bytes.  "Slot tails": bytes [16 CD, stride) of a
+ *     delivered row are not written.
+ *  7. Overflow.  Entries with j >= max_out are not written anywhere.
+ *
+ * Written: first_of [G + 1], *n_out, and seg / seg_payload as rule 6 says.
+ * Nothing else: entries at and past min(T, max_out) keep what they held, every
+ * input is untouched, and the payload bytes of an out slot whose out_index is
+ * 0xFF are not read.  Consistency of the tables is the caller's to keep: as
+ * rfec_wire_regroup_shapes writes them, sections[p].group_of[rank_of[g]] == g
+ * for every decoded g.  The delivery goes by group_of: a value >= G there
+ * (RFEC_REGROUP_NONE, as the rows past counts[p] hold) delivers nothing, and a
+ * row that disagrees with rank_of gives unspecified entries -- never a read or
+ * a write outside the arrays as sized here.
+ *
+ * workspace: rfec_recover_deliver_workspace_size(G) bytes (a multiple of 16),
+ * 16-byte aligned; it needs no initialisation.
+ *
+ * Checked before any runtime call (RFEC_EINVAL, rfec_last_error names the
+ * argument), in this order: plans not NULL; n_plans in [1,
+ * RFEC_RECOVER_MAX_SHAPES]; sections not NULL (but see window_groups == 0);
+ * each plan; window_groups <= 65535; fec_id0 != 0; stride a positive multiple
+ * of 16; capacity <= stride; per_group >= 1; groups[p] <= sections[p].cap;
+ * R * per_group * CD < 2^31 and R < 2^32.  window_groups == 0 then touches
+ * nothing: every pointer but plans may be NULL.  Then NULL pointers (seg and
+ * seg_payload may be NULL when max_out == 0; out_shards, out_hdr and out_index
+ * when R == 0; sections[p].group_of when groups[p] == 0) and alignment: 16
+ * bytes out_shards, seg_payload and workspace; 4 bytes out_hdr, seg, rank_of,
+ * first_of, n_out and every group_of.  With G > 0 and R == 0 the call still
+ * writes first_of[0..G] = 0 and *n_out = 0.  The buffers must not overlap (not
+ * checked).  The call allocates nothing, copies nothing from the host (the
+ * sections' group_of pointers and first[] travel as kernel arguments), does
+ * not synchronise and launches only on `stream`: three launches, two when
+ * window_groups <= 256, none waiting on another workgroup.
+ */
+size_t rfec_recover_deliver_workspace_size(uint32_t window_groups);
+
+int rfec_recover_deliver(const rfec_plan* plans, uint32_t n_plans,            /* host */
+                         const rfec_regroup_section* sections,                /* host, of device pointers: group_of is read */
+                         const uint32_t* groups,                              /* host [n_plans] or NULL: sections[p].cap */
+                         uint32_t window_groups, uint16_t fec_id0,
+                         const uint8_t* shape_of, const uint32_t* rank_of,    /* device [G], as regroup_shapes wrote them */
+                         uint32_t stride, uint32_t capacity, uint32_t per_group,
+                         const uint8_t* out_shards, const rfec_hdr* out_hdr,  /* device: the decode's outputs */
+                         const uint8_t* out_index,
+                         uint32_t max_out,
+                         rfec_rx_seg* seg, uint8_t* seg_payload,              /* device [max_out], [max_out][stride] */
+                         uint32_t* first_of,                                  /* device [G + 1] */
+                         uint32_t* n_out,                                     /* device [1] */
+                         void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------ */
 /* Sender staging: sim_sender_put (sim_sender.c:306-377) with sim_split_frame */
 /* (:254-284) and the flex sender's grouping (flex_fec_sender.c:49-78,       */
@@ -1107,11 +1196,7 @@ int rfec_host_send_frames(rfec_sender_state* st, const rfec_frame* frames, uint3
 /* row * col < count) and parities inconsistent with their members.         */
 /* Output: the recovered segments, ascending packet_id.                     */
 /* ------------------------------------------------------------------------ */
-typedef struct {
-    rfec_hdr hdr;     /* recovered header (flex_fec_xor.c:64-85) */
-    uint16_t fec_id;  /* out_seg->fec_id = fec->fec_id (:101) */
-    uint16_t reserved;
-} rfec_rx_seg; /* 24 bytes */
+/* (rfec_rx_seg, the record of a delivered segment: above, at rfec_recover_deliver) */
 
 typedef struct {
     uint32_t n_groups, n_shapes, n_recovered, n_fec_dropped, n_unmodelled, reserved;

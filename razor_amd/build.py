@@ -30,7 +30,8 @@ ARCH = os.environ.get("RFEC_OFFLOAD_ARCH", "gfx950")
 # families -- encode, peel + replay, fused disjoint decodes, cascade / matrix decodes, the receiver's helpers --
 # are a unit each, reached through the host functions rfec_families.h declares
 HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused", "cascade", "helpers", "probe",
-                                             "wire", "fill", "service", "hostio", "regroup", "regroup_shapes")]
+                                             "wire", "fill", "service", "hostio", "regroup", "regroup_shapes",
+                                             "deliver")]
 # built once per SIM_VIDEO_SIZE: the C host layer, by concern (rfec_host.c: errors, planner, batched device
 # and wire API; rfec_dropin.c: drop-in symbols + resident service; rfec_hostmem.c: host-memory batches;
 # rfec_sender.c: sender staging; the receiver: rfec_rx_sim.c one shard's arrival-order control plane,
@@ -41,7 +42,8 @@ HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused"
 # a window of several shapes) and
 # rfec_recover_indexed.c (the dense decode through a row map), rfec_recover_indexed_matrix.c (its one-launch form
 # for the sender's matrix plans) and rfec_recover_indexed_shapes.c (its one-launch form for a window's sections of
-# several shapes) call launch shims of their own,
+# several shapes) and rfec_recover_deliver.c (that decode's outputs as a list of delivered segments in window order,
+# kernels in rfec_deliver.hip) call launch shims of their own,
 # so they stay out of HOST_SRC: the CPU builds of the host layer compile exactly HOST_SRC against a stub of the runtime
 HOST_NOHIP_SRC = ["rfec_rx_sim.c", "rfec_rx_pool.c", "rfec_rx_plane.c"]  # no GPU runtime: built and tested alone
 HOST_SRC = ["rfec_host.c", "rfec_dropin.c", "rfec_hostmem.c", "rfec_sender.c", *HOST_NOHIP_SRC, "rfec_rx_dev.c",
@@ -49,7 +51,7 @@ HOST_SRC = ["rfec_host.c", "rfec_dropin.c", "rfec_hostmem.c", "rfec_sender.c", *
 C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packed_matrix.c",
                                           CSRC / "rfec_wire_fused.c", CSRC / "rfec_wire_regroup.c",
                                           CSRC / "rfec_recover_indexed.c", CSRC / "rfec_recover_indexed_matrix.c",
-                                          CSRC / "rfec_recover_indexed_shapes.c"]
+                                          CSRC / "rfec_recover_indexed_shapes.c", CSRC / "rfec_recover_deliver.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h", CSRC / "rfec_device.h", CSRC / "rfec_families.h",

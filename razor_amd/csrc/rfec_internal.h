@@ -234,13 +234,27 @@ int rfec_launch_recover_indexed_shapes(const rfec_kplan* plans, uint32_t n_plans
  * 16-byte chunks of work per slot); 0 for a plan of neither shape */
 uint32_t rfec_recover_shapes_blocks(const rfec_kplan* P, uint32_t groups, uint32_t per_group, uint32_t cd,
                                     uint32_t n_rows);
-/* Which kernels the calling thread's last rfec_launch_recover_indexed, rfec_launch_recover_indexed_matrix or
- * rfec_launch_recover_indexed_shapes took (host-side, thread-local, for tests; apart from rfec_last_path, whose
- * kinds are a closed table): 0 none yet,
+/* rfec_recover_deliver (rfec_recover_deliver.c, kernels in rfec_deliver.hip): the outputs of
+ * rfec_launch_recover_indexed_shapes as a dense list in window order, in three launches on `stream` (k_deliver_count,
+ * k_deliver_totals, k_deliver), two when groups <= 256 (one block counts the window and writes the totals).  first:
+ * host [n_plans + 1], the prefix of the sections' rows as that decode numbers them; workspace: local[groups] u32,
+ * then from the next multiple of 16 bytes one u32 per 256 groups.  The caller has checked n_plans in
+ * [1, RFEC_RECOVER_MAX_SHAPES], groups in [1, 65535], fec_id0 != 0, stride a multiple of 16, capacity <= stride,
+ * per_group >= 1, first[n_plans] * per_group * CD < 2^31 and the pointers; hipErrorInvalidValue otherwise. */
+int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n_plans, const uint32_t* first,
+                                uint32_t groups, uint32_t fec_id0, const uint8_t* shape_of, const uint32_t* rank_of,
+                                uint32_t stride, uint32_t capacity, uint32_t per_group, const uint8_t* out_shards,
+                                const rfec_hdr* out_hdr, const uint8_t* out_index, uint32_t max_out, rfec_rx_seg* seg,
+                                uint8_t* seg_payload, uint32_t* first_of, uint32_t* n_out, void* workspace,
+                                void* stream);
+/* Which kernels the calling thread's last rfec_launch_recover_indexed, rfec_launch_recover_indexed_matrix,
+ * rfec_launch_recover_indexed_shapes or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
+ * from rfec_last_path, whose kinds are a closed table): 0 none yet,
  * 1 | K << 8 one launch of k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8
  * k_peel_lds + k_recover_indexed<MAXC, ...> (MAXC = 4, 8), 3 | K << 8 one launch of k_decode_matrix_indexed<K, col>
  * (K = 6..16; rfec_launch_recover_indexed_matrix only), 4 | n << 8 one launch of k_decode_shapes_indexed over n
- * sections with groups (rfec_launch_recover_indexed_shapes only). */
+ * sections with groups (rfec_launch_recover_indexed_shapes only), 5 | n << 8 the n = 2 or 3 launches of
+ * rfec_launch_recover_deliver (k_deliver_count, k_deliver_totals for a window of more than 256 groups, k_deliver). */
 uint32_t rfec_indexed_last_path(void);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */

@@ -1,7 +1,8 @@
 // rfec_regroup_rules.h -- the placement rules of razor_fec.h ("The placement rule") as device code, one copy for
 // rfec_regroup.hip (one shape) and rfec_regroup_shapes.hip (a window of several): how a parsed record is read,
 // which records take part, the group a fec_id names, and what the winner of a slot and the slots of a group leave
-// in the tables.  C++ only, not installed; everything is forced inline.
+// in the tables.  rfec_deliver.hip takes the window's succession of fec_ids from here.  C++ only, not installed;
+// everything is forced inline.
 #ifndef RFEC_REGROUP_RULES_H_
 #define RFEC_REGROUP_RULES_H_
 
@@ -50,6 +51,13 @@ __device__ __forceinline__ uint32_t group_of(uint32_t fec_id, uint32_t fec_id0, 
         return kNone;
     const uint32_t g = fec_id >= fec_id0 ? fec_id - fec_id0 : fec_id + 65535u - fec_id0;
     return g < groups ? g : kNone;
+}
+
+// its inverse: the fec_id of window group g < 65535, ((fec_id0 - 1 + g) % 65535) + 1 (rfec_recover_deliver's entries)
+__device__ __forceinline__ uint32_t fec_id_of(uint32_t fec_id0, uint32_t g)
+{
+    const uint32_t id = fec_id0 + g;
+    return id > 65535u ? id - 65535u : id;
 }
 
 // a slot's lane: the header record of the slot's winner (w: the winner's record as words) to h, and a parity's

@@ -279,6 +279,10 @@ _SIGS = {
     "rfec_recover_indexed_shapes_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
                                                   C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_uint32, _P,
                                                   C.c_uint32, _P, _P, _P, _P]),
+    "rfec_recover_deliver_workspace_size": (C.c_size_t, [C.c_uint32]),
+    "rfec_recover_deliver": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
+                                       C.POINTER(C.c_uint32), C.c_uint32, C.c_uint16, _P, _P, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "rfec_host_send_frames": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
@@ -608,6 +612,29 @@ class Native:
         self._check(self.lib.rfec_recover_indexed_shapes_out(pa, len(plans), sa, ga, stride, capacity, rows, n_rows,
                                                              recovered, per_group, out_shards, out_hdr, out_index,
                                                              stream), "rfec_recover_indexed_shapes_out")
+
+    def recover_deliver_workspace_size(self, window_groups) -> int:
+        return int(self.lib.rfec_recover_deliver_workspace_size(window_groups))
+
+    def recover_deliver(self, plans, sections, groups, G, fec_id0, shape_of, rank_of, stride, capacity, per_group,
+                        out_shards, out_hdr, out_index, max_out, seg, seg_payload, first_of, n_out, workspace,
+                        stream=None):
+        """rfec_recover_deliver: what recover_indexed_shapes_out wrote (the same plans / sections / groups /
+        per_group; G, fec_id0, shape_of and rank_of those of wire_regroup_shapes) as a dense list in window order:
+        seg [max_out] (RX_SEG_DTYPE) and seg_payload [max_out][stride], first_of [G + 1] and n_out [1] (u32,
+        neither clamped to max_out); workspace: recover_deliver_workspace_size(G) bytes."""
+        if len(plans) != len(sections):
+            raise ValueError("one section per plan")
+        if groups is not None and len(groups) != len(plans):
+            raise ValueError("one group count per plan")
+        pa = (rfec_plan * max(len(plans), 1))(*(as_plan(p) for p in plans))
+        sa = (rfec_regroup_section * max(len(sections), 1))(
+            *(s if isinstance(s, rfec_regroup_section) else rfec_regroup_section(**s) for s in sections))
+        ga = None if groups is None else (C.c_uint32 * max(len(groups), 1))(*(int(g) for g in groups))
+        self._check(self.lib.rfec_recover_deliver(pa, len(plans), sa, ga, G, fec_id0, shape_of, rank_of, stride,
+                                                  capacity, per_group, out_shards, out_hdr, out_index, max_out, seg,
+                                                  seg_payload, first_of, n_out, workspace, stream),
+                    "rfec_recover_deliver")
 
     # -- sender staging (host memory) -------------------------------------------
     def sender_init(self):
