@@ -401,7 +401,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_shapes_out, rfec_recover_deliver) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_matrix_wide_out, rfec_recover_indexed_shapes_out, rfec_recover_deliver) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -933,6 +933,53 @@ int rfec_recover_indexed_matrix_out(const rfec_plan* plan, uint32_t groups, uint
                                     const rfec_hdr* meta, const uint16_t* fec_size, const uint64_t* parity_present,
                                     uint64_t* recovered, uint32_t per_group,
                                     uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index, void* stream);
+
+/*
+ * rfec_recover_indexed_matrix_out for the sender's full row + column plan of
+ * any k in [6, RFEC_MAX_K]: the plan rfec_plan_from_fraction(k, pf >= 10,
+ * RFEC_LAYER_ROWS | RFEC_LAYER_COLS) returns -- rows of `col` consecutive
+ * segments, then the `col` columns, col from rfec_num_packets (3..12; a last
+ * row of one segment has no line: up to 23 lines of up to 12 members).  That
+ * is every frame of 6 or more segments once protect_fraction >= 10, an
+ * I-frame of 100 segments included.  One launch, no workspace, nothing
+ * staged; the shape is taken at run time (one kernel for every k, masks of
+ * two 64-bit words).  Any other plan gets RFEC_EINVAL -- a full matrix in rows
+ * of another width, rows or columns alone, a row layout, a strip plan -- and
+ * its caller uses rfec_recover_indexed_out, which takes every plan.
+ * rfec_recover_indexed_matrix_out (k = 6..16, the shape compiled in) and
+ * rfec_recover_indexed_shapes_out keep their own answers.
+ *
+ * Results: recovered (both words: k may pass 64), out_index, out_hdr, and
+ * out_shards over [0, 16 CD) of every slot whose out_index is not 0xFF, are
+ * byte for byte what rfec_recover_indexed_out writes for the same arguments
+ * (so what rfec_recover_batch_out writes on the gathered batch: cascades of
+ * any depth, lines the header checks refuse and the rescheduling around them,
+ * and dense mode's rule that only erased segments of rank < per_group are
+ * targets, included).  Bytes [16 CD, stride) of every out slot are not
+ * written; payload bytes of a slot whose out_index is 0xFF are unspecified.
+ * Every input is untouched; the map's consistency rule, the clamp of a row
+ * index to n_rows - 1 and the 64-bit row addresses are
+ * rfec_recover_indexed_out's.  With n_rows == 0 no row is read: recovered,
+ * out_hdr and out_index are still written.  rfec_set_tuning does not reach
+ * this call.
+ *
+ * Checked before any runtime call (RFEC_EINVAL), in
+ * rfec_recover_indexed_matrix_out's order: the plan and its shape, stride a
+ * positive multiple of 16, capacity <= stride, per_group in [1, k],
+ * groups * per_group * CD < 2^31, NULL pointers (rows may be NULL when
+ * n_rows == 0), alignment: 16 bytes rows and out_shards; 8 bytes present,
+ * parity_present and recovered; 4 bytes src_of, hdr, meta and out_hdr; 2 bytes
+ * fec_size (one checker lane per group: their count is bounded with the
+ * groups).  groups == 0 touches nothing: every pointer may be NULL.  The call allocates
+ * nothing, does not synchronise and launches only on `stream`; no workgroup
+ * waits on another.
+ */
+int rfec_recover_indexed_matrix_wide_out(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                         const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of,
+                                         const rfec_hdr* hdr, const uint64_t* present,
+                                         const rfec_hdr* meta, const uint16_t* fec_size, const uint64_t* parity_present,
+                                         uint64_t* recovered, uint32_t per_group,
+                                         uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index, void* stream);
 
 /*
  * The decode behind rfec_wire_regroup_shapes: the sections of a closed window

@@ -215,6 +215,21 @@ int rfec_launch_recover_indexed_matrix(const rfec_kmask* M, uint32_t groups, uin
                                        const rfec_hdr* hdr, const uint64_t* present, const rfec_hdr* meta,
                                        const uint16_t* fsize, const uint64_t* parity_present, uint64_t* recovered,
                                        const rfec_dense_out* out, void* stream);
+/* 1 when P is the sender's full row + column plan of its k in rows of `col` (is_full_matrix, rfec_kernels.hip: the
+ * rows of col consecutive segments in plan order, then the columns, lines of fewer than 2 members dropped), else 0 */
+int rfec_full_matrix(const rfec_kplan* P, uint32_t col);
+/* rfec_recover_indexed_matrix_wide_out (rfec_recover_indexed_matrix_wide.c, kernel in rfec_matrix_wide.hip): the
+ * same decode for the sender's full row + column plan of any k in [6, RFEC_MAX_K] in rows of `col`, the planner's
+ * (rfec_full_matrix(P, col) != 0, col in [3, 20], at most 23 lines), in one launch of k_decode_matrix_wide, which
+ * takes (k, col) at run time; no workspace; with n_rows == 0 the checker blocks alone.  The caller has checked
+ * what rfec_launch_recover_indexed_matrix's has, with one checker lane per group (groups < 2^32 as it stands);
+ * hipErrorInvalidValue otherwise.  No flags: rfec_set_tuning does not reach this call. */
+int rfec_launch_recover_indexed_matrix_wide(const rfec_kplan* P, uint32_t col, uint32_t groups, uint32_t stride,
+                                            uint32_t capacity, const uint8_t* rows, uint32_t n_rows,
+                                            const uint32_t* src_of, const rfec_hdr* hdr, const uint64_t* present,
+                                            const rfec_hdr* meta, const uint16_t* fsize,
+                                            const uint64_t* parity_present, uint64_t* recovered,
+                                            const rfec_dense_out* out, void* stream);
 /* The plans rfec_launch_recover_indexed runs in one launch of k_decode_rows_indexed: the row width of a row layout
  * with rows of <= 4 segments and k <= 64, 0 for any other plan. */
 int rfec_rows_indexed_col(const rfec_kplan* P);
@@ -248,13 +263,14 @@ int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n
                                 uint8_t* seg_payload, uint32_t* first_of, uint32_t* n_out, void* workspace,
                                 void* stream);
 /* Which kernels the calling thread's last rfec_launch_recover_indexed, rfec_launch_recover_indexed_matrix,
- * rfec_launch_recover_indexed_shapes or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
+ * rfec_launch_recover_indexed_matrix_wide, rfec_launch_recover_indexed_shapes or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
  * from rfec_last_path, whose kinds are a closed table): 0 none yet,
  * 1 | K << 8 one launch of k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8
  * k_peel_lds + k_recover_indexed<MAXC, ...> (MAXC = 4, 8), 3 | K << 8 one launch of k_decode_matrix_indexed<K, col>
  * (K = 6..16; rfec_launch_recover_indexed_matrix only), 4 | n << 8 one launch of k_decode_shapes_indexed over n
  * sections with groups (rfec_launch_recover_indexed_shapes only), 5 | n << 8 the n = 2 or 3 launches of
- * rfec_launch_recover_deliver (k_deliver_count, k_deliver_totals for a window of more than 256 groups, k_deliver). */
+ * rfec_launch_recover_deliver (k_deliver_count, k_deliver_totals for a window of more than 256 groups, k_deliver),
+ * 6 | k << 8 one launch of k_decode_matrix_wide (k = 6..128; rfec_launch_recover_indexed_matrix_wide only). */
 uint32_t rfec_indexed_last_path(void);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */

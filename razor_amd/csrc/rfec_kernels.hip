@@ -10,8 +10,9 @@
 //    * otherwise (and RFEC_TUNE_GENERIC): the peel and the replay of rfec_peel.hip;
 //  recover through a slot map over a row pool (rfec_launch_recover_indexed, dense output only): row layouts in
 //  one launch (rfec_fused.hip), every other plan the peel and an indexed replay (rfec_peel.hip).  (The sender's
-//  matrix plans in one launch are an entry point of their own, rfec_launch_recover_indexed_matrix in
-//  rfec_cascade.hip: this dispatch does not pick it.)
+//  matrix plans in one launch are entry points of their own, rfec_launch_recover_indexed_matrix in
+//  rfec_cascade.hip for k = 6..16 and rfec_launch_recover_indexed_matrix_wide in rfec_matrix_wide.hip for any
+//  k = 6..128: this dispatch does not pick them.)
 #include "rfec_families.h"
 
 static thread_local hipEvent_t t_ev_start = nullptr, t_ev_stop = nullptr;
@@ -271,6 +272,8 @@ int rfec_packed_matrix_col(const rfec_kplan* P)
     const uint32_t k = P->k, col = k <= 9 ? 3u : 4u;
     return k >= 6 && k <= 16 && is_full_matrix(P, col) ? (int)col : 0;
 }
+
+int rfec_full_matrix(const rfec_kplan* P, uint32_t col) { return col && is_full_matrix(P, col) ? 1 : 0; }
 
 const char* rfec_hip_error_string(int code) { return hipGetErrorString((hipError_t)code); }
 

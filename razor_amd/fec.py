@@ -276,6 +276,9 @@ _SIGS = {
                                            _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "rfec_recover_indexed_matrix_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P,
                                                   C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
+    "rfec_recover_indexed_matrix_wide_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                                       C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P,
+                                                       _P]),
     "rfec_recover_indexed_shapes_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
                                                   C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_uint32, _P,
                                                   C.c_uint32, _P, _P, _P, _P]),
@@ -595,6 +598,17 @@ class Native:
                                                              n_rows, src_of, hdr, present, meta, fec_size,
                                                              parity_present, recovered, per_group, out_shards, out_hdr,
                                                              out_index, stream), "rfec_recover_indexed_matrix_out")
+
+    def recover_indexed_matrix_wide_out(self, plan, groups, stride, capacity, rows, n_rows, src_of, hdr, present, meta,
+                                        fec_size, parity_present, recovered, per_group, out_shards, out_hdr,
+                                        out_index, stream=None):
+        """rfec_recover_indexed_matrix_wide_out: recover_indexed_out for the sender's full row + column plan of any
+        k = 6..128 (plan_from_fraction(k, pf >= 10, ROWS | COLS)) in one launch, without a workspace."""
+        self._check(self.lib.rfec_recover_indexed_matrix_wide_out(C.byref(as_plan(plan)), groups, stride, capacity,
+                                                                  rows, n_rows, src_of, hdr, present, meta, fec_size,
+                                                                  parity_present, recovered, per_group, out_shards,
+                                                                  out_hdr, out_index, stream),
+                    "rfec_recover_indexed_matrix_wide_out")
 
     def recover_indexed_shapes_out(self, plans, sections, groups, stride, capacity, rows, n_rows, recovered,
                                    per_group, out_shards, out_hdr, out_index, stream=None):
