@@ -401,7 +401,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_matrix_wide_out, rfec_recover_indexed_shapes_out, rfec_recover_deliver) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_matrix_wide_out, rfec_recover_indexed_rows_wide_out, rfec_recover_indexed_shapes_out, rfec_recover_deliver) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -980,6 +980,61 @@ int rfec_recover_indexed_matrix_wide_out(const rfec_plan* plan, uint32_t groups,
                                          const rfec_hdr* meta, const uint16_t* fec_size, const uint64_t* parity_present,
                                          uint64_t* recovered, uint32_t per_group,
                                          uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index, void* stream);
+
+/*
+ * rfec_recover_indexed_out without `workspace` and in one launch for a row
+ * layout of any width: with col = line[0].count >= 2, line l is (first l col,
+ * stride 1, count min(col, k - l col)) for l = 0 .. n_lines - 1, and n_lines
+ * is ceil(k / col) -- or one less when the last row has one segment: that row
+ * has no line and its segment is never recovered.  k in [2, RFEC_MAX_K], col
+ * up to 128, up to RFEC_MAX_LINES rows.  That is every strip-mode plan of
+ * rfec_plan_from_fraction (protect_fraction < 10, and every group of fewer
+ * than 6 segments: one parity over the frame, or rows of ceil(k / lines)
+ * segments), rfec_plan_matrix(k, row, col, RFEC_LAYER_ROWS), the rows-only
+ * layer of a full matrix, and the row layouts rfec_recover_indexed_out itself
+ * decodes in one launch.  The shape is taken at run time (one kernel, masks of
+ * two 64-bit words).  Any other plan gets RFEC_EINVAL -- a full matrix, columns
+ * alone, a plan without lines, rows with a gap or of unequal width, a
+ * hand-made plan -- and its caller uses rfec_recover_indexed_out, which takes
+ * every plan.  rfec_recover_indexed_out, rfec_recover_indexed_shapes_out and
+ * both matrix entries keep their own answers and kernels for every plan.
+ *
+ * Results: recovered (both words), out_index, out_hdr, and out_shards over
+ * [0, 16 CD) of every slot whose out_index is not 0xFF, are byte for byte what
+ * rfec_recover_indexed_out writes for the same arguments (dense mode's rule
+ * that only erased segments of rank < per_group are targets, and lines the
+ * header checks refuse, included).  Bytes [16 CD, stride) of every out slot
+ * are not written; payload bytes of a slot whose out_index is 0xFF are
+ * unspecified.  Every input is untouched; the map's consistency rule, the
+ * clamp of a row index to n_rows - 1 and the 64-bit row addresses are
+ * rfec_recover_indexed_out's.  With n_rows == 0 no row is read: recovered,
+ * out_hdr and out_index are still written.  rfec_set_tuning does not reach
+ * this call.
+ *
+ * In a window of several shapes (rfec_wire_regroup_shapes) a section with such
+ * a plan that rfec_recover_indexed_shapes_out does not take is decoded as a
+ * wide matrix section is: groups[p] = 0 in the window decode, this call on the
+ * section's tables with its outputs at row first[p] of the same dense arrays
+ * (recovered + 2 first[p], out_index + first[p] per_group, ...), then
+ * rfec_recover_deliver with groups[p] = min(counts[p], cap).
+ *
+ * Checked before any runtime call (RFEC_EINVAL), in rfec_recover_indexed_out's
+ * order and with its messages: the plan and, right after it, its shape;
+ * stride a positive multiple of 16, capacity <= stride, per_group in [1, k],
+ * groups * per_group * CD < 2^31, NULL pointers (rows may be NULL when
+ * n_rows == 0; meta and fec_size are never optional), alignment: 16 bytes rows
+ * and out_shards; 8 bytes present, parity_present and recovered; 4 bytes
+ * src_of, hdr, meta and out_hdr; 2 bytes fec_size, and last the header lanes'
+ * bound, groups * 2^ceil(log2(max(n_lines, 2))) < 2^32.  groups == 0 touches
+ * nothing: every pointer may be NULL.  The call allocates nothing, does not
+ * synchronise and launches only on `stream`; no workgroup waits on another.
+ */
+int rfec_recover_indexed_rows_wide_out(const rfec_plan* plan, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                       const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of,
+                                       const rfec_hdr* hdr, const uint64_t* present,
+                                       const rfec_hdr* meta, const uint16_t* fec_size, const uint64_t* parity_present,
+                                       uint64_t* recovered, uint32_t per_group,
+                                       uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index, void* stream);
 
 /*
  * The decode behind rfec_wire_regroup_shapes: the sections of a closed window

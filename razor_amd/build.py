@@ -31,7 +31,7 @@ ARCH = os.environ.get("RFEC_OFFLOAD_ARCH", "gfx950")
 # are a unit each, reached through the host functions rfec_families.h declares
 HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused", "cascade", "helpers", "probe",
                                              "wire", "fill", "service", "hostio", "regroup", "regroup_shapes",
-                                             "deliver", "matrix_wide")]
+                                             "deliver", "matrix_wide", "rows_wide")]
 # built once per SIM_VIDEO_SIZE: the C host layer, by concern (rfec_host.c: errors, planner, batched device
 # and wire API; rfec_dropin.c: drop-in symbols + resident service; rfec_hostmem.c: host-memory batches;
 # rfec_sender.c: sender staging; the receiver: rfec_rx_sim.c one shard's arrival-order control plane,
@@ -42,7 +42,8 @@ HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused"
 # a window of several shapes) and
 # rfec_recover_indexed.c (the dense decode through a row map), rfec_recover_indexed_matrix.c (its one-launch form
 # for the sender's matrix plans of k = 6..16; rfec_recover_indexed_matrix_wide.c: for those of any k = 6..128, kernel
-# in rfec_matrix_wide.hip) and rfec_recover_indexed_shapes.c (its one-launch form for a window's sections of
+# in rfec_matrix_wide.hip; rfec_recover_indexed_rows_wide.c: for a row layout of any width, kernel in
+# rfec_rows_wide.hip) and rfec_recover_indexed_shapes.c (its one-launch form for a window's sections of
 # several shapes) and rfec_recover_deliver.c (that decode's outputs as a list of delivered segments in window order,
 # kernels in rfec_deliver.hip) call launch shims of their own,
 # so they stay out of HOST_SRC: the CPU builds of the host layer compile exactly HOST_SRC against a stub of the runtime
@@ -53,7 +54,8 @@ C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packe
                                           CSRC / "rfec_wire_fused.c", CSRC / "rfec_wire_regroup.c",
                                           CSRC / "rfec_recover_indexed.c", CSRC / "rfec_recover_indexed_matrix.c",
                                           CSRC / "rfec_recover_indexed_shapes.c", CSRC / "rfec_recover_deliver.c",
-                                          CSRC / "rfec_recover_indexed_matrix_wide.c"]
+                                          CSRC / "rfec_recover_indexed_matrix_wide.c",
+                                          CSRC / "rfec_recover_indexed_rows_wide.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h", CSRC / "rfec_device.h", CSRC / "rfec_families.h",

@@ -4,7 +4,8 @@
  * rfec_hostmem.c, rfec_sender.c, rfec_rx_dev.c, rfec_rx_session.c,
  * rfec_packed_matrix.c, rfec_wire_fused.c, rfec_wire_regroup.c,
  * rfec_recover_indexed.c, rfec_recover_indexed_matrix.c,
- * rfec_recover_indexed_matrix_wide.c, rfec_recover_indexed_shapes.c,
+ * rfec_recover_indexed_matrix_wide.c, rfec_recover_indexed_rows_wide.c,
+ * rfec_recover_indexed_shapes.c,
  * rfec_recover_deliver.c; the
  * receiver's host-only units rfec_rx_sim.c, rfec_rx_pool.c, rfec_rx_plane.c
  * do without it).  Internal: hidden from the shared library's exports.

@@ -230,6 +230,20 @@ int rfec_launch_recover_indexed_matrix_wide(const rfec_kplan* P, uint32_t col, u
                                             const rfec_hdr* meta, const uint16_t* fsize,
                                             const uint64_t* parity_present, uint64_t* recovered,
                                             const rfec_dense_out* out, void* stream);
+/* rfec_recover_indexed_rows_wide_out (rfec_recover_indexed_rows_wide.c, kernel in rfec_rows_wide.hip): the same
+ * decode for a row layout of any width in one launch of k_decode_rows_wide, which takes (k, col, n_lines) at run
+ * time; no workspace; with n_rows == 0 the header blocks alone.  rfec_rows_wide_col is the predicate: the row width
+ * col = line[0].count >= 2 when line l is (l col, stride 1, min(col, k - l col)) for every l < n_lines and n_lines is
+ * ceil(k / col), or one less when the last row has one segment (it has no line); 0 for any other plan.  The tables'
+ * pitch is k + n_lines (src_of) and n_lines (meta, fsize).  The caller has checked what
+ * rfec_launch_recover_indexed's has (groups << rfec_header_lanes_log2(n_lines) < 2^32 among it);
+ * hipErrorInvalidValue otherwise.  No flags: rfec_set_tuning does not reach this call. */
+int rfec_rows_wide_col(const rfec_kplan* P);
+int rfec_launch_recover_indexed_rows_wide(const rfec_kplan* P, uint32_t groups, uint32_t stride, uint32_t capacity,
+                                          const uint8_t* rows, uint32_t n_rows, const uint32_t* src_of,
+                                          const rfec_hdr* hdr, const uint64_t* present, const rfec_hdr* meta,
+                                          const uint16_t* fsize, const uint64_t* parity_present, uint64_t* recovered,
+                                          const rfec_dense_out* out, void* stream);
 /* The plans rfec_launch_recover_indexed runs in one launch of k_decode_rows_indexed: the row width of a row layout
  * with rows of <= 4 segments and k <= 64, 0 for any other plan. */
 int rfec_rows_indexed_col(const rfec_kplan* P);
@@ -263,14 +277,17 @@ int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n
                                 uint8_t* seg_payload, uint32_t* first_of, uint32_t* n_out, void* workspace,
                                 void* stream);
 /* Which kernels the calling thread's last rfec_launch_recover_indexed, rfec_launch_recover_indexed_matrix,
- * rfec_launch_recover_indexed_matrix_wide, rfec_launch_recover_indexed_shapes or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
+ * rfec_launch_recover_indexed_matrix_wide, rfec_launch_recover_indexed_rows_wide, rfec_launch_recover_indexed_shapes
+ * or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
  * from rfec_last_path, whose kinds are a closed table): 0 none yet,
  * 1 | K << 8 one launch of k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8
  * k_peel_lds + k_recover_indexed<MAXC, ...> (MAXC = 4, 8), 3 | K << 8 one launch of k_decode_matrix_indexed<K, col>
  * (K = 6..16; rfec_launch_recover_indexed_matrix only), 4 | n << 8 one launch of k_decode_shapes_indexed over n
  * sections with groups (rfec_launch_recover_indexed_shapes only), 5 | n << 8 the n = 2 or 3 launches of
  * rfec_launch_recover_deliver (k_deliver_count, k_deliver_totals for a window of more than 256 groups, k_deliver),
- * 6 | k << 8 one launch of k_decode_matrix_wide (k = 6..128; rfec_launch_recover_indexed_matrix_wide only). */
+ * 6 | k << 8 one launch of k_decode_matrix_wide (k = 6..128; rfec_launch_recover_indexed_matrix_wide only),
+ * 7 | k << 8 | col << 16 one launch of k_decode_rows_wide (k = 2..128 in rows of col = 2..128;
+ * rfec_launch_recover_indexed_rows_wide only). */
 uint32_t rfec_indexed_last_path(void);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */

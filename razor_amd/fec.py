@@ -279,6 +279,9 @@ _SIGS = {
     "rfec_recover_indexed_matrix_wide_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P,
                                                        C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P,
                                                        _P]),
+    "rfec_recover_indexed_rows_wide_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                                     C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P,
+                                                     _P]),
     "rfec_recover_indexed_shapes_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
                                                   C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_uint32, _P,
                                                   C.c_uint32, _P, _P, _P, _P]),
@@ -609,6 +612,17 @@ class Native:
                                                                   parity_present, recovered, per_group, out_shards,
                                                                   out_hdr, out_index, stream),
                     "rfec_recover_indexed_matrix_wide_out")
+
+    def recover_indexed_rows_wide_out(self, plan, groups, stride, capacity, rows, n_rows, src_of, hdr, present, meta,
+                                      fec_size, parity_present, recovered, per_group, out_shards, out_hdr, out_index,
+                                      stream=None):
+        """rfec_recover_indexed_rows_wide_out: recover_indexed_out for a row layout of any width (the strip-mode
+        plans of plan_from_fraction, plan_matrix(k, row, col, ROWS)) in one launch, without a workspace."""
+        self._check(self.lib.rfec_recover_indexed_rows_wide_out(C.byref(as_plan(plan)), groups, stride, capacity,
+                                                                rows, n_rows, src_of, hdr, present, meta, fec_size,
+                                                                parity_present, recovered, per_group, out_shards,
+                                                                out_hdr, out_index, stream),
+                    "rfec_recover_indexed_rows_wide_out")
 
     def recover_indexed_shapes_out(self, plans, sections, groups, stride, capacity, rows, n_rows, recovered,
                                    per_group, out_shards, out_hdr, out_index, stream=None):
