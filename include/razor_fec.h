@@ -465,7 +465,9 @@ typedef struct {
  * `status` may be NULL; a slot with status -1 gets length 0 (the reference
  * never emits that parity).  `order` may be NULL; otherwise datagram i is
  * written to slot order[i] of dgram / dlen (a permutation).  Needs
- * fec_size <= capacity <= stride and dstride >= capacity + 49.  Datagram
+ * fec_size <= capacity <= stride and dstride >= capacity + 49.
+ * Alignment (RFEC_EINVAL for less): 16 bytes parity and dgram, 4 bytes meta,
+ * stamps and order, 2 bytes fec_size and dlen (status: any).  Datagram
  * slots whose stride is a multiple of 128 bytes (1,280 for 1,200-byte
  * payloads) are written in whole 128-byte lines: 0.60 of HBM peak against
  * 0.52 for the minimal 16-byte multiples, whose slot edges split lines
@@ -479,7 +481,9 @@ int rfec_wire_frame_fec(uint32_t count, uint32_t stride, uint32_t capacity, cons
  * sim_proto.inl:83-125; header widths follow the value ranges) of `count`
  * segments: shards [count][stride], hdr [count]; `order` as for
  * rfec_wire_frame_fec.  Needs data_size <= capacity <= stride and
- * dstride >= capacity + 36. */
+ * dstride >= capacity + 36.
+ * Alignment (RFEC_EINVAL for less): 16 bytes shards and dgram, 4 bytes hdr,
+ * stamps and order, 2 bytes dlen. */
 int rfec_wire_frame_seg(uint32_t count, uint32_t stride, uint32_t capacity, const uint8_t* shards,
                         const rfec_hdr* hdr, const rfec_seg_stamp* stamps, const uint32_t* order, uint32_t dstride,
                         uint8_t* dgram, uint16_t* dlen, void* stream);
@@ -645,7 +649,9 @@ typedef struct {
  * sim_decode_msg) into recs [N] and their payloads into slots [N][stride]
  * (zero beyond data_size: the layout rfec_recover_batch expects).  `capacity`
  * plays SIM_VIDEO_SIZE in the length checks (cf_stream.c:342-355,
- * sim_proto.inl:301-305); capacity <= stride. */
+ * sim_proto.inl:301-305); capacity <= stride.
+ * Alignment (RFEC_EINVAL for less): 16 bytes dgram, recs and payload, 2 bytes
+ * dlen. */
 int rfec_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const uint16_t* dlen,
                     uint32_t stride, uint32_t capacity, rfec_wire_rec* recs, uint8_t* payload,
                     void* stream);

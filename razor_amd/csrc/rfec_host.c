@@ -490,6 +490,13 @@ int rfec_wire_frame_fec(uint32_t count, uint32_t stride, uint32_t capacity, cons
         return RFEC_OK;
     if (!parity || !meta || !fec_size || !stamps || !dgram || !dlen)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    /* (a NULL status or order is aligned) */
+    if (misaligned(parity, 16) || misaligned(dgram, 16))
+        return set_err(RFEC_EINVAL, "parity and dgram must be 16-byte aligned", 0);
+    if (misaligned(meta, 4) || misaligned(stamps, 4) || misaligned(order, 4))
+        return set_err(RFEC_EINVAL, "meta, stamps and order must be 4-byte aligned", 0);
+    if (misaligned(fec_size, 2) || misaligned(dlen, 2))
+        return set_err(RFEC_EINVAL, "fec_size and dlen must be 2-byte aligned", 0);
     const int e = rfec_launch_wire_frame_fec(count, stride, capacity, parity, meta, fec_size, status, stamps,
                                              order, dstride, dgram, dlen, stream);
     return e ? set_err(RFEC_EDEVICE, "wire_frame_fec launch", e) : RFEC_OK;
@@ -506,6 +513,12 @@ int rfec_wire_frame_seg(uint32_t count, uint32_t stride, uint32_t capacity, cons
         return RFEC_OK;
     if (!shards || !hdr || !stamps || !dgram || !dlen)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if (misaligned(shards, 16) || misaligned(dgram, 16))
+        return set_err(RFEC_EINVAL, "shards and dgram must be 16-byte aligned", 0);
+    if (misaligned(hdr, 4) || misaligned(stamps, 4) || misaligned(order, 4)) /* (a NULL order is aligned) */
+        return set_err(RFEC_EINVAL, "hdr, stamps and order must be 4-byte aligned", 0);
+    if (misaligned(dlen, 2))
+        return set_err(RFEC_EINVAL, "dlen must be 2-byte aligned", 0);
     const int e = rfec_launch_wire_frame_seg(count, stride, capacity, shards, hdr, stamps, order, dstride, dgram,
                                              dlen, count, stream);
     return e ? set_err(RFEC_EDEVICE, "wire_frame_seg launch", e) : RFEC_OK;
@@ -530,6 +543,10 @@ int rfec_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const ui
         return RFEC_OK;
     if (!dgram || !dlen || !recs || !payload)
         return set_err(RFEC_EINVAL, "NULL buffer", 0);
+    if (misaligned(dgram, 16) || misaligned(recs, 16) || misaligned(payload, 16))
+        return set_err(RFEC_EINVAL, "dgram, recs and payload must be 16-byte aligned", 0);
+    if (misaligned(dlen, 2))
+        return set_err(RFEC_EINVAL, "dlen must be 2-byte aligned", 0);
     const int e = rfec_launch_wire_parse(n, dstride, dgram, dlen, stride, capacity, recs, payload, 0, stream);
     return e ? set_err(RFEC_EDEVICE, "wire_parse launch", e) : RFEC_OK;
 }

@@ -289,6 +289,40 @@ int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n
  * 7 | k << 8 | col << 16 one launch of k_decode_rows_wide (k = 2..128 in rows of col = 2..128;
  * rfec_launch_recover_indexed_rows_wide only). */
 uint32_t rfec_indexed_last_path(void);
+/* Which kernel the calling thread's last wire-codec launch (rfec_wire.hip: the rfec_launch_wire_* shims) took, and on
+ * how many blocks: kernel id | grid blocks << 8, 0 before the first (host-side, thread-local, for tests; apart from
+ * rfec_last_path and rfec_indexed_last_path, which keep their own tags).  A wave of the kernel then strides over its
+ * units by nw = 16 * blocks.  A call that takes several launches (the fused encodes split a batch past 32-bit
+ * offsets) leaves its last launch's tag.  The ids:
+ *   FRAME_FEC_32 / FRAME_SEG_32    k_frame_fec<32> / k_frame_seg<32>: dstride > 1,280, a datagram per wave step
+ *   PARSE_20 / PARSE_32            k_parse<20> / k_parse<32>: a datagram per wave step (RFEC_TUNE_WAVE_PARSE, or
+ *                                  slots or payload slots past 1,280 bytes)
+ *   FRAME_SEG_Q / FRAME_FEC_Q      k_frame_seg_q / k_frame_fec_q: a quad of 4 datagrams per wave step
+ *   PARSE_Q                        k_parse_q: a quad per wave step, header batches of 16 quads
+ *   ENCODE_FEC_Q                   k_encode_frame_fec_q (rfec_wire_encode_fec): a quad of SIM_FEC per wave step
+ *   ENCODE_SEND_Q / _Q2            k_encode_send_q<., 5> / <., 2> (dstride <= 512): 4 groups per wave step
+ *   ENCODE_SEND_SHAPES_Q / _Q2     k_encode_send_shapes_q<., 5> / <., 2> (dstride <= 512): 4 descriptors per step */
+enum {
+    RFEC_WIRE_K_NONE = 0,
+    RFEC_WIRE_K_FRAME_FEC_32 = 1,
+    RFEC_WIRE_K_FRAME_SEG_32 = 3,
+    RFEC_WIRE_K_PARSE_20 = 4,
+    RFEC_WIRE_K_PARSE_32 = 5,
+    RFEC_WIRE_K_FRAME_SEG_Q = 6,
+    RFEC_WIRE_K_FRAME_FEC_Q = 7,
+    RFEC_WIRE_K_PARSE_Q = 8,
+    RFEC_WIRE_K_ENCODE_FEC_Q = 9,
+    RFEC_WIRE_K_ENCODE_SEND_Q = 10,
+    RFEC_WIRE_K_ENCODE_SEND_Q2 = 11,
+    RFEC_WIRE_K_ENCODE_SEND_SHAPES_Q = 12,
+    RFEC_WIRE_K_ENCODE_SEND_SHAPES_Q2 = 13
+};
+uint32_t rfec_wire_last_path(void);
+/* For tests: at most `blocks` blocks for every wire-codec launch from now on, in every thread (0, the default: none
+ * -- the grid is the resident blocks or what the batch needs, whichever is less; the cap is taken after that).  A
+ * small cap makes a small batch walk the persistent loops as deep as a large batch does on the whole device.  One
+ * word, read once per launch; no environment variable. */
+void rfec_wire_set_grid_cap(uint32_t blocks);
 /* max_len: the longest datagram when the caller knows it (host-side lengths), else 0; slots
  * wider than 1,280 B still take the 20-byte-lane parse when every datagram fits 1,280 B */
 int rfec_launch_wire_parse(uint32_t n, uint32_t dstride, const uint8_t* dgram, const uint16_t* dlen,

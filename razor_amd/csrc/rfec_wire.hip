@@ -2657,9 +2657,34 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))) voi
 
 // Persistent grid: exactly the blocks that are resident at once (occupancy
 // from the kernel's registers / LDS x CUs), so no block waits for a second
-// round; fewer when the batch is small.  TAG: one cache per kernel instance.
+// round; fewer when the batch is small.  TAG: one cache per kernel instance,
+// and the kernel's id in rfec_wire_last_path (RFEC_WIRE_K_*, rfec_internal.h).
+// g_grid_cap (rfec_wire_set_grid_cap, for tests): at most that many blocks; 0: no cap.
+uint32_t g_grid_cap = 0;
+thread_local uint32_t t_wire_path = 0;
+static_assert(RFEC_WIRE_K_FRAME_FEC_32 == 1 && RFEC_WIRE_K_FRAME_SEG_32 == 3 && RFEC_WIRE_K_PARSE_20 == 4 &&
+                  RFEC_WIRE_K_PARSE_32 == 5 && RFEC_WIRE_K_FRAME_SEG_Q == 6 && RFEC_WIRE_K_FRAME_FEC_Q == 7 &&
+                  RFEC_WIRE_K_PARSE_Q == 8 && RFEC_WIRE_K_ENCODE_FEC_Q == 9 && RFEC_WIRE_K_ENCODE_SEND_Q == 10 &&
+                  RFEC_WIRE_K_ENCODE_SEND_Q2 == 11 && RFEC_WIRE_K_ENCODE_SEND_SHAPES_Q == 12 &&
+                  RFEC_WIRE_K_ENCODE_SEND_SHAPES_Q2 == 13,
+              "the launches' grid_for<TAG> below are these ids");
+
+template <int TAG>
+uint32_t grid_for_resident(const void* kernel, uint32_t count);
+
 template <int TAG>
 uint32_t grid_for(const void* kernel, uint32_t count)
+{
+    uint32_t grid = grid_for_resident<TAG>(kernel, count);
+    const uint32_t cap = g_grid_cap;
+    if (cap && cap < grid)
+        grid = cap;
+    t_wire_path = (uint32_t)TAG | grid << 8;
+    return grid;
+}
+
+template <int TAG>
+uint32_t grid_for_resident(const void* kernel, uint32_t count)
 {
     static int resident = 0; // blocks per device, per kernel
     if (!resident) {
@@ -2690,6 +2715,9 @@ inline bool quarter_ok(uint32_t count, uint32_t stride, uint32_t dstride)
 } // namespace
 
 extern "C" {
+
+void rfec_wire_set_grid_cap(uint32_t blocks) { g_grid_cap = blocks; }
+uint32_t rfec_wire_last_path(void) { return t_wire_path; }
 
 int rfec_launch_wire_frame_fec(uint32_t count, uint32_t stride, uint32_t capacity, const uint8_t* parity,
                                const rfec_hdr* meta, const uint16_t* fec_size, const int8_t* status,

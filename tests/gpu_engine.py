@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 import guarded_arena as ga
+import wire_cases as wc
 from razor_amd.fec import HDR_DTYPE, native
 
 
@@ -171,55 +172,63 @@ class GpuEngine(ga.ArenaEngine):
                 A.get("packed", np.uint8, (G, pks)))
 
 
-class GpuWire:
-    """The wire codec (rfec_wire_*) on numpy inputs."""
+class GpuWire(wc.WireEngine):
+    """The wire codec (rfec_wire_frame_fec / _seg, rfec_wire_parse and rfec_launch_wire_parse_split) on numpy
+    inputs, every call's buffers in one guarded arena (wire_cases.WireEngine: each pointer at exactly its documented
+    alignment, the outputs between canary guards, the inputs compared with what was uploaded).  last_path:
+    rfec_wire_last_path's tag of the call (kernel id | grid blocks << 8, rfec_internal.h)."""
+
+    has_tag = True
 
     def __init__(self, video_size=1000, device="cuda:0", tuning=0):
+        import aux_kernel_cases as ac
         self.lib = native(video_size)
+        self.c = ac.bind_launches(self.lib.lib)
+        self.c.rfec_wire_last_path.restype, self.c.rfec_wire_last_path.argtypes = C.c_uint32, []
+        self.c.rfec_wire_set_grid_cap.restype, self.c.rfec_wire_set_grid_cap.argtypes = None, [C.c_uint32]
         self.device = torch.device(device)
+        self.be = TorchBackend(self.device)
         self.tuning = tuning  # RFEC_TUNE_WAVE_PARSE: the wave-per-datagram parse
 
-    def _run(self, fn, *args):
-        fn(*args, torch.cuda.current_stream(self.device).cuda_stream)
-        torch.cuda.synchronize(self.device)
+    def set_grid_cap(self, blocks):
+        """rfec_wire_set_grid_cap: process-global; the caller restores 0 in a finally."""
+        self.c.rfec_wire_set_grid_cap(blocks)
 
-    def frame_fec(self, parity, meta, fsize, status, stamps, capacity, dstride):
-        N, stride = parity.shape[0] if parity.ndim == 2 else parity.size // parity.shape[-1], parity.shape[-1]
-        d_p, d_m, d_f, d_s = (_dev(a, self.device) for a in (parity, meta, np.ascontiguousarray(fsize, np.uint16),
-                                                                stamps))
-        d_st = None if status is None else _dev(np.ascontiguousarray(status, np.int8), self.device)
-        d_g = torch.full((N * dstride,), 0xEE, dtype=torch.uint8, device=self.device)
-        d_l = torch.full((N,), 0x7777, dtype=torch.int16, device=self.device)
-        self._run(self.lib.wire_frame_fec, N, stride, capacity, d_p.data_ptr(), d_m.data_ptr(), d_f.data_ptr(),
-                  None if d_st is None else d_st.data_ptr(), d_s.data_ptr(), dstride, d_g.data_ptr(), d_l.data_ptr())
-        return _host(d_g, np.uint8, (N, dstride)), _host(d_l, np.uint16, (N,))
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
 
-    def frame_seg(self, shards, hdr, stamps, capacity, dstride, order=None):
-        stride = shards.shape[-1]
-        N = shards.size // stride
-        d_d, d_h, d_s = (_dev(a, self.device) for a in (shards, hdr, stamps))
-        d_o = None if order is None else _dev(np.ascontiguousarray(order, np.uint32), self.device)
-        d_g = torch.full((N * dstride,), 0xEE, dtype=torch.uint8, device=self.device)
-        d_l = torch.full((N,), 0x7777, dtype=torch.int16, device=self.device)
-        fn = lambda *a: self.lib.wire_frame_seg(*a, order=None if d_o is None else d_o.data_ptr())  # noqa: E731
-        self._run(fn, N, stride, capacity, d_d.data_ptr(), d_h.data_ptr(), d_s.data_ptr(), dstride, d_g.data_ptr(),
-                  d_l.data_ptr())
-        return _host(d_g, np.uint8, (N, dstride)), _host(d_l, np.uint16, (N,))
+    def _ran(self):
+        self.last_path = int(self.c.rfec_wire_last_path())
 
-    def parse(self, dgram, dlen, stride, capacity):
-        N, dstride = dgram.shape
-        d_g = _dev(dgram, self.device)
-        d_l = _dev(np.ascontiguousarray(dlen, np.uint16), self.device)
-        d_r = torch.full((N * 64,), 0xEE, dtype=torch.uint8, device=self.device)
-        d_p = torch.full((N * stride,), 0xEE, dtype=torch.uint8, device=self.device)
-        self.lib.set_tuning(self.tuning)
+    @staticmethod
+    def _opt(A, name):
+        return A.ptr(name) if name in A.bufs else None
+
+    def _frame_fec(self, A, N, stride, capacity, dstride):
+        self.lib.wire_frame_fec(N, stride, capacity, A.ptr("parity"), A.ptr("meta"), A.ptr("fec_size"),
+                                self._opt(A, "status"), A.ptr("stamps"), dstride, A.ptr("dgram"), A.ptr("dlen"),
+                                self._stream(), order=self._opt(A, "order"))
+        self._ran()
+
+    def _frame_seg(self, A, N, stride, capacity, dstride):
+        self.lib.wire_frame_seg(N, stride, capacity, A.ptr("shards"), A.ptr("hdr"), A.ptr("stamps"), dstride,
+                                A.ptr("dgram"), A.ptr("dlen"), self._stream(), order=self._opt(A, "order"))
+        self._ran()
+
+    def _parse(self, A, N, dstride, stride, capacity, T, max_len, tuning):
+        self.lib.set_tuning(self.tuning if tuning is None else tuning)
         try:
-            self._run(self.lib.wire_parse, N, dstride, d_g.data_ptr(), d_l.data_ptr(), stride, capacity,
-                      d_r.data_ptr(), d_p.data_ptr())
+            if T is None:
+                self.lib.wire_parse(N, dstride, A.ptr("dgram"), A.ptr("dlen"), stride, capacity, A.ptr("recs"),
+                                    A.ptr("payload"), self._stream())
+            else:
+                rc = self.c.rfec_launch_wire_parse_split(N, dstride, A.ptr("dgram"), A.ptr("dlen"), stride, capacity,
+                                                         A.ptr("recs"), A.ptr("payload"), max_len, A.ptr("split"), T,
+                                                         self._stream())
+                assert rc == 0, ("rfec_launch_wire_parse_split", rc)
+            self._ran()
         finally:
             self.lib.set_tuning(0)
-        from razor_amd.fec import WIRE_REC_DTYPE
-        return _host(d_r, WIRE_REC_DTYPE, (N,)), _host(d_p, np.uint8, (N, stride))
 
 
 class GpuAux:
@@ -237,6 +246,7 @@ class GpuAux:
         self.c.hipHostGetDevicePointer.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint]
         self.device = torch.device(device)
         self.pinned = pinned
+        self.wire = None  # parse_split's engine
 
     def _canary(self, nbytes):
         return torch.full((nbytes,), self.ac.CANARY, dtype=torch.uint8, device=self.device)
@@ -309,20 +319,8 @@ class GpuAux:
         return _host(d_o, np.uint8, (slots + self.ac.GUARD, stride))
 
     def parse_split(self, dgram, dlen, stride, capacity, max_len, T, tuning=0):
-        """rfec_launch_wire_parse_split: (recs, payload, split entries + GUARD), the split buffer pre-filled
-        with 0xAB."""
-        from razor_amd.fec import WIRE_REC_DTYPE
-        N, dstride = dgram.shape
-        d_g = _dev(dgram, self.device)
-        d_l = _dev(np.ascontiguousarray(dlen, np.uint16), self.device)
-        d_r = torch.full((N * 64,), 0xEE, dtype=torch.uint8, device=self.device)
-        d_p = torch.full((N * stride,), 0xEE, dtype=torch.uint8, device=self.device)
-        d_s = torch.full(((N + self.ac.GUARD) * 8,), 0xAB, dtype=torch.uint8, device=self.device)
-        self.lib.set_tuning(tuning)
-        try:
-            self._run(self.c.rfec_launch_wire_parse_split, N, dstride, d_g.data_ptr(), d_l.data_ptr(), stride,
-                      capacity, d_r.data_ptr(), d_p.data_ptr(), max_len, d_s.data_ptr(), T)
-        finally:
-            self.lib.set_tuning(0)
-        return (_host(d_r, WIRE_REC_DTYPE, (N,)), _host(d_p, np.uint8, (N, stride)),
-                _host(d_s, self.ac.SPLIT_DTYPE, (N + self.ac.GUARD,)))
+        """rfec_launch_wire_parse_split through GpuWire's guarded arena: (recs, payload, split entries + GUARD),
+        the split buffer pre-filled with 0xAB."""
+        if self.wire is None:
+            self.wire = GpuWire(self.lib.video_size, self.device)
+        return self.wire.parse_split(dgram, dlen, stride, capacity, max_len, T, tuning, tail=self.ac.GUARD)

@@ -14,18 +14,7 @@ import pyoracle as po
 import wire_cases as wc
 
 
-class OracleWire:
-    def __init__(self, o):
-        self.o = o
-
-    def frame_fec(self, parity, meta, fsize, status, stamps, capacity, dstride):
-        return self.o.frame_fec_batch(parity, meta, fsize, status, stamps, capacity, dstride)
-
-    def frame_seg(self, shards, hdr, stamps, capacity, dstride):
-        return self.o.frame_seg_batch(shards, hdr, stamps, capacity, dstride)
-
-    def parse(self, dgram, dlen, stride, capacity):
-        return self.o.parse_batch(dgram, dlen, stride, capacity)
+OracleWire = wc.OracleWire  # the oracle behind the guarded arenas the GPU engine uses (wire_cases.WireEngine)
 
 
 # -- CPU: oracle pinned to the reference ---------------------------------------
@@ -68,6 +57,177 @@ def test_wire_short_datagram_oracle(oracle1000):
     dgram = np.zeros((4, 64), np.uint8)
     recs, _ = oracle1000.parse_batch(dgram, np.array([0, 1, 2, 3], np.uint16), wc.STRIDE, wc.CAP)
     assert (recs["status"] == -1).all()
+
+
+# -- CPU: the guarded engine's checks can each fail ------------------------------
+def test_wire_engine_checks_can_fail(oracle1000):
+    """On the oracle's run of the engine: one changed guard byte after each output, one changed input byte, and --
+    in the comparisons the loop cases use -- one changed datagram byte, length and record byte are each reported."""
+    import wire_loop_cases as wl
+    rng = np.random.default_rng(7)
+    N, capacity, stride, dstride = 9, 230, 240, 288
+    data, hdr, sizes, stamps = wc.random_batch(rng, N, stride, capacity, seg=True)
+    eng = OracleWire(oracle1000)
+    g, gl = eng.frame_seg(data, hdr, stamps, capacity, dstride, order=np.arange(N, dtype=np.uint32))
+    o, ol = oracle1000.frame_seg_batch(data, hdr, stamps, capacity, dstride)
+    wl.same_frames(g, gl, o, ol, "oracle run")
+    recs, pay, split = eng.parse_split(g, gl, stride, capacity, 0, 3)
+    orecs, opay = oracle1000.parse_batch(g, gl, stride, capacity)
+    wl.same_parse(recs, pay, orecs, opay, "oracle run")
+    wl.same_split(split, orecs, 3, "oracle run")
+    assert (recs["status"] == 0).all() and np.array_equal(pay, np.where(np.arange(stride) < sizes[:, None], data, 0))
+
+    g2 = g.copy()
+    g2[N - 1, int(gl[N - 1]) + 1] ^= 1  # a byte past the datagram's length: whole slots are compared
+    with pytest.raises(AssertionError, match="slots differ"):
+        wl.same_frames(g2, gl, o, ol, "changed datagram byte")
+    gl2 = gl.copy()
+    gl2[3] += 1
+    with pytest.raises(AssertionError, match="lengths differ"):
+        wl.same_frames(g, gl2, o, ol, "changed length")
+    r2 = recs.copy()
+    r2.view(np.uint8).reshape(N, 64)[5, 63] ^= 1  # a reserved byte: all 64 are compared
+    with pytest.raises(AssertionError, match="records differ"):
+        wl.same_parse(r2, pay, orecs, opay, "changed record byte")
+    p2 = pay.copy()
+    p2[0, stride - 1] ^= 1
+    with pytest.raises(AssertionError, match="payload slots differ"):
+        wl.same_parse(recs, p2, orecs, opay, "changed payload byte")
+    s2 = split.copy()
+    s2["reserved"][N - 1] = 1
+    with pytest.raises(AssertionError, match="split entries differ"):
+        wl.same_split(s2, orecs, 3, "changed split byte")
+
+    def after(name):
+        def mutate(A, what):
+            A.mem[A.bufs[name].off + A.bufs[name].nbytes] ^= 1  # the first byte past the buffer
+        return mutate
+
+    def inside(name, at):
+        def mutate(A, what):
+            A.view(name)[at] ^= 1
+        return mutate
+
+    calls = {
+        "frame_seg": lambda: eng.frame_seg(data, hdr, stamps, capacity, dstride, order=np.arange(N, dtype=np.uint32)),
+        "frame_fec": lambda: eng.frame_fec(data, hdr, sizes, np.zeros(N, np.int8), stamps_fec, capacity, dstride),
+        "parse": lambda: eng.parse(g, gl, stride, capacity),
+        "parse_split": lambda: eng.parse_split(g, gl, stride, capacity, 0, 3),
+    }
+    _, _, _, stamps_fec = wc.random_batch(rng, N, stride, capacity, seg=False)
+    for call, mutate, msg in (
+            ("frame_seg", after("dgram"), "guard after dgram"), ("frame_seg", after("dlen"), "guard after dlen"),
+            ("frame_fec", after("dgram"), "guard after dgram"), ("frame_fec", after("dlen"), "guard after dlen"),
+            ("parse", after("recs"), "guard after recs"), ("parse", after("payload"), "guard after payload"),
+            ("parse_split", after("split"), "guard after split"),
+            ("frame_seg", inside("shards", 17), "input shards was written"),
+            ("frame_seg", inside("order", 4), "input order was written"),
+            ("frame_fec", inside("status", N - 1), "input status was written"),
+            ("frame_fec", inside("fec_size", 2), "input fec_size was written"),
+            ("parse", inside("dgram", 100), "input dgram was written"),
+            ("parse_split", inside("dlen", 1), "input dlen was written")):
+        eng.mutate = mutate
+        with pytest.raises(AssertionError, match=msg):
+            calls[call]()
+    eng.mutate = None
+    # every pointer of a call at exactly its documented alignment and nothing larger
+    eng.parse_split(g, gl, stride, capacity, 0, 3)
+    A = eng.last_arena
+    for name, b in A.bufs.items():
+        assert b.align == wc.WIRE_ALIGN[name] and A.ptr(name) % b.align == 0 and A.ptr(name) % (2 * b.align) != 0, name
+
+
+# -- CPU: the three entries' argument checks, through the host stub (no device) ---------------------------------------
+@pytest.fixture(scope="module")
+def stub(tmp_path_factory):
+    import ctypes as C
+
+    from host_stub_build import build_stub_library, have_hip_headers
+    from razor_amd import fec
+    if not have_hip_headers():
+        pytest.skip("HIP headers not available")
+    lib = C.CDLL(str(build_stub_library(tmp_path_factory.mktemp("wirestub") / "librazor_fec_wirestub.so")))
+    for fn in ("rfec_wire_frame_fec", "rfec_wire_frame_seg", "rfec_wire_parse", "rfec_last_error"):
+        f = getattr(lib, fn)
+        f.restype, f.argtypes = fec._SIGS[fn]
+    return lib
+
+
+# addresses that are never dereferenced: the stub's launches do nothing, the checks come before them
+P16, P4, P2, P1 = 0x10000, 0x20004, 0x30002, 0x40001
+WIRE_ARGS = {
+    "rfec_wire_frame_fec": (("count", 8), ("stride", 1216), ("capacity", 1200), ("parity", P16), ("meta", P4),
+                            ("fec_size", P2), ("status", P1), ("stamps", P4 + 0x100), ("order", P4 + 0x200),
+                            ("dstride", 1264), ("dgram", P16 + 0x1000), ("dlen", P2 + 0x100)),
+    "rfec_wire_frame_seg": (("count", 8), ("stride", 1216), ("capacity", 1200), ("shards", P16), ("hdr", P4),
+                            ("stamps", P4 + 0x100), ("order", P4 + 0x200), ("dstride", 1264), ("dgram", P16 + 0x1000),
+                            ("dlen", P2 + 0x100)),
+    "rfec_wire_parse": (("n", 8), ("dstride", 1264), ("dgram", P16), ("dlen", P2), ("stride", 1216),
+                        ("capacity", 1200), ("recs", P16 + 0x1000), ("payload", P16 + 0x2000)),
+}
+WIRE_MISALIGNED = {
+    "rfec_wire_frame_fec": {"parity": (8, "parity and dgram must be 16-byte aligned"),
+                            "dgram": (8, "parity and dgram must be 16-byte aligned"),
+                            "meta": (2, "meta, stamps and order must be 4-byte aligned"),
+                            "stamps": (2, "meta, stamps and order must be 4-byte aligned"),
+                            "order": (2, "meta, stamps and order must be 4-byte aligned"),
+                            "fec_size": (1, "fec_size and dlen must be 2-byte aligned"),
+                            "dlen": (1, "fec_size and dlen must be 2-byte aligned")},
+    "rfec_wire_frame_seg": {"shards": (8, "shards and dgram must be 16-byte aligned"),
+                            "dgram": (8, "shards and dgram must be 16-byte aligned"),
+                            "hdr": (2, "hdr, stamps and order must be 4-byte aligned"),
+                            "stamps": (2, "hdr, stamps and order must be 4-byte aligned"),
+                            "order": (2, "hdr, stamps and order must be 4-byte aligned"),
+                            "dlen": (1, "dlen must be 2-byte aligned")},
+    "rfec_wire_parse": {"dgram": (8, "dgram, recs and payload must be 16-byte aligned"),
+                        "recs": (8, "dgram, recs and payload must be 16-byte aligned"),
+                        "payload": (8, "dgram, recs and payload must be 16-byte aligned"),
+                        "dlen": (1, "dlen must be 2-byte aligned")},
+}
+
+
+def _wire_call(stub, fn, **kw):
+    args = [kw.get(name, v) for name, v in WIRE_ARGS[fn]]
+    rc = getattr(stub, fn)(*args, None)
+    return rc, stub.rfec_last_error().decode()
+
+
+@pytest.mark.parametrize("fn", sorted(WIRE_ARGS))
+def test_wire_alignment_checks(stub, fn):
+    """Each pointer one step below its documented alignment is RFEC_EINVAL with a message that names it; the
+    checks come after the geometry and NULL checks, widest alignment first, are skipped for count == 0 and pass a
+    NULL status / order and a status at any address."""
+    base = dict(WIRE_ARGS[fn])
+    rc, err = _wire_call(stub, fn)
+    assert rc == 0, err
+    optional = [a for a in ("status", "order") if a in base]
+    rc, err = _wire_call(stub, fn, **{a: None for a in optional})
+    assert rc == 0, err
+    for arg, (off, msg) in WIRE_MISALIGNED[fn].items():
+        rc, err = _wire_call(stub, fn, **{arg: base[arg] + off})
+        assert rc == -1 and msg in err and arg in msg, (arg, rc, err)
+        # at the documented alignment and nothing larger: accepted
+        align = 2 * off
+        rc, err = _wire_call(stub, fn, **{arg: (base[arg] & ~0xFF) + align})
+        assert rc == 0, (arg, err)
+    # order: geometry, then NULL, then 16, 4, 2 bytes
+    first16 = next(a for a, (off, _) in WIRE_MISALIGNED[fn].items() if off == 8)
+    first2 = next(a for a, (off, _) in WIRE_MISALIGNED[fn].items() if off == 1)
+    bad16, bad2 = {first16: base[first16] + 8}, {first2: base[first2] + 1}
+    rc, err = _wire_call(stub, fn, dstride=1265, **bad16)
+    assert rc == -1 and "dstride must be a multiple of 16" in err, err
+    rc, err = _wire_call(stub, fn, dlen=None, **bad16)
+    assert rc == -1 and "NULL buffer" in err, err
+    rc, err = _wire_call(stub, fn, **bad16, **({} if first2 in bad16 else bad2))
+    assert rc == -1 and "16-byte" in err, err
+    first4 = [a for a, (off, _) in WIRE_MISALIGNED[fn].items() if off == 2]
+    if first4:
+        rc, err = _wire_call(stub, fn, **{first4[0]: base[first4[0]] + 2}, **bad2)
+        assert rc == -1 and "4-byte" in err, err
+    # nothing to do: nothing is looked at
+    count = WIRE_ARGS[fn][0][0]
+    rc, err = _wire_call(stub, fn, **{count: 0}, **bad16, **bad2)
+    assert rc == 0, err
 
 
 # -- GPU -----------------------------------------------------------------------

@@ -41,6 +41,9 @@ PLANS = {
     "k1": lambda o: wec._hand_plan(1, []),                            # no line: segments only
     "k255": wec.PLANS["k255"],                                        # a strip of all 255 members
 }
+# plans of the capped-grid loop cases (wire_loop_cases.py) alone: a line of 18 members is two SIM_SEG header batches
+# of 16 in k_encode_send_q / k_encode_send_shapes_q, beside a line of 2
+LOOP_PLANS = {"row18k20": lambda o: wec._hand_plan(20, [(0, 1, 18), (18, 1, 2)])}
 
 # (capacity, stride, dstride); "p": every shard byte in [16 CD, stride) poisoned
 GEOMS = {
@@ -98,7 +101,7 @@ def make_inputs(oracle, c):
     """The case's inputs and what the oracle composed expects of them."""
     pname, gname, G, with_so, with_fo = c
     capacity, stride, dstride = GEOMS[gname]
-    plan = PLANS[pname](oracle)
+    plan = (PLANS.get(pname) or LOOP_PLANS[pname])(oracle)
     k, n = plan.k, plan.n_lines
     rng = np.random.default_rng(zlib.crc32(case_id(c).encode()))
     N = G * k

@@ -105,7 +105,7 @@ def make_inputs(oracle, name, c=None):
     """The case's inputs, its descriptors and what the oracle composed per shape expects of them."""
     shapes, gname, seq, layout, dorder, with_so, with_fo = c if c is not None else CASES[name]
     capacity, stride, dstride = GEOMS[gname]
-    plans = [PLANS[s](oracle) for s in shapes]
+    plans = [(PLANS.get(s) or wsc.LOOP_PLANS[s])(oracle) for s in shapes]
     rng = np.random.default_rng(zlib.crc32(name.encode()))
     G = len(seq)
     big = G > 5000  # the loop case: cheap inputs
