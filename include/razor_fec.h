@@ -1104,6 +1104,73 @@ int rfec_recover_indexed_shapes_out(const rfec_plan* plans, uint32_t n_plans,
                                     uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index,
                                     void* stream);
 
+/*
+ * rfec_recover_indexed_shapes_out for a window of ANY of the planner's shapes:
+ * the same arguments, the same output numbering (row c of section p is output
+ * row first[p] + c, one per_group for the call, recovered indexed by output
+ * row) and the same NULL rules, so rfec_recover_deliver takes its outputs
+ * unchanged, with the same plans, sections, groups and per_group.  No section
+ * of a planner plan has to sit in the window with groups[p] = 0 and take a
+ * launch of its own: strip-mode frames and the frames above 16 segments decode
+ * in the window's one launch.
+ *
+ * The family of a section with groups[p] > 0 is the first of these that holds:
+ *  1. the sender's full row + column plan of k = 6..16
+ *     (rfec_packed_matrix_stride(plan, 1) != 0), decoded as
+ *     rfec_recover_indexed_matrix_out decodes it (the shape compiled in);
+ *  2. a row layout of rows of <= 4 segments with k <= 64, as
+ *     rfec_recover_indexed_out decodes it in one launch;
+ *  3. the sender's full row + column plan of k = 17..128 in rows of
+ *     rfec_num_packets' col (at most 23 lines), as
+ *     rfec_recover_indexed_matrix_wide_out decodes it;
+ *  4. any other row layout -- k in [2, RFEC_MAX_K], rows of 2..128, a last row
+ *     of one segment without a line -- as rfec_recover_indexed_rows_wide_out
+ *     decodes it.
+ * Any other plan gets RFEC_EINVAL and rfec_last_error names plans[p]: a
+ * hand-made plan, columns alone, rows with a gap or of unequal width, a plan
+ * without lines.  Give that section groups[p] == 0 and decode it with
+ * rfec_recover_indexed_out.  A section with groups[p] == 0 only has to hold a
+ * valid plan; its tables may be NULL.
+ *
+ * Results: for every p with groups[p] > 0, output rows [first[p], first[p] +
+ * groups[p]) hold byte for byte what its family's single-shape call (above)
+ * writes into arrays of its own for (&plans[p], groups[p], stride, capacity,
+ * rows, n_rows, section p's tables, per_group): recovered, out_index, out_hdr,
+ * and out_shards over [0, 16 CD) of every slot whose out_index is not 0xFF.
+ * Bytes [16 CD, stride) of every out slot are not written; the payload of a
+ * 0xFF slot is unspecified; every input is untouched.  The clamp of a row
+ * index to n_rows - 1, the 64-bit row addresses and n_rows == 0 (only the
+ * header and checker lanes run, no row is read: recovered, out_hdr and
+ * out_index are still written) are those calls'.  A wide section keeps its
+ * table pitch: k + n_lines map words and n_lines meta records per group.
+ * rfec_set_tuning does not reach this call.
+ *
+ * Checked before any runtime call (RFEC_EINVAL), in
+ * rfec_recover_indexed_shapes_out's order: plans not NULL, n_plans in [1,
+ * RFEC_RECOVER_MAX_SHAPES], sections not NULL, each plan and, with
+ * groups[p] > 0, its family; stride a positive multiple of 16,
+ * capacity <= stride, per_group in [1, the least k of the sections with
+ * groups]; per section groups[p] <= cap, groups[p] * per_group * CD < 2^31 and
+ * the header lanes' bound of its family (1: groups * 4 < 2^32; 2 and 4:
+ * groups * 2^ceil(log2(max(n_lines, 2))) < 2^32; 3: one checker lane per group,
+ * no further bound); the launch's blocks (the sections' own grids, end to end)
+ * < 2^31 and its output rows < 2^32.  All groups[p] == 0 touches nothing:
+ * every other pointer may be NULL.  Then NULL pointers (rows may be NULL when
+ * n_rows == 0) and alignment: 16 bytes rows and out_shards; 8 bytes present,
+ * parity_present and recovered; 4 bytes src_of, hdr, meta and out_hdr; 2 bytes
+ * fec_size.  The call uses no workspace, allocates nothing, copies nothing from
+ * the host (the sections travel as kernel arguments), does not synchronise and
+ * makes exactly one launch on `stream`; no workgroup waits on another.
+ */
+int rfec_recover_indexed_window_out(const rfec_plan* plans, uint32_t n_plans,
+                                    const rfec_regroup_section* sections,
+                                    const uint32_t* groups, /* host [n_plans], or NULL: sections[p].cap */
+                                    uint32_t stride, uint32_t capacity,
+                                    const uint8_t* rows, uint32_t n_rows,
+                                    uint64_t* recovered, uint32_t per_group,
+                                    uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index,
+                                    void* stream);
+
 /* One delivered segment, as every call that hands recovered segments back
  * writes it (rfec_recover_deliver below; rfec_rx_recover, the rx session). */
 typedef struct {

@@ -44,7 +44,8 @@ HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused"
 # for the sender's matrix plans of k = 6..16; rfec_recover_indexed_matrix_wide.c: for those of any k = 6..128, kernel
 # in rfec_matrix_wide.hip; rfec_recover_indexed_rows_wide.c: for a row layout of any width, kernel in
 # rfec_rows_wide.hip) and rfec_recover_indexed_shapes.c (its one-launch form for a window's sections of
-# several shapes) and rfec_recover_deliver.c (that decode's outputs as a list of delivered segments in window order,
+# several shapes; rfec_recover_indexed_window.c: for a window of any of the planner's shapes, the wide kernels' bodies
+# shared through rfec_matrix_wide_blocks.h and rfec_rows_wide_blocks.h) and rfec_recover_deliver.c (that decode's outputs as a list of delivered segments in window order,
 # kernels in rfec_deliver.hip) call launch shims of their own,
 # so they stay out of HOST_SRC: the CPU builds of the host layer compile exactly HOST_SRC against a stub of the runtime
 HOST_NOHIP_SRC = ["rfec_rx_sim.c", "rfec_rx_pool.c", "rfec_rx_plane.c"]  # no GPU runtime: built and tested alone
@@ -55,11 +56,13 @@ C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packe
                                           CSRC / "rfec_recover_indexed.c", CSRC / "rfec_recover_indexed_matrix.c",
                                           CSRC / "rfec_recover_indexed_shapes.c", CSRC / "rfec_recover_deliver.c",
                                           CSRC / "rfec_recover_indexed_matrix_wide.c",
-                                          CSRC / "rfec_recover_indexed_rows_wide.c"]
+                                          CSRC / "rfec_recover_indexed_rows_wide.c",
+                                          CSRC / "rfec_recover_indexed_window.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h", CSRC / "rfec_device.h", CSRC / "rfec_families.h",
-           CSRC / "rfec_row_blocks.h", CSRC / "rfec_regroup_rules.h"]
+           CSRC / "rfec_row_blocks.h", CSRC / "rfec_regroup_rules.h", CSRC / "rfec_u128.h",
+           CSRC / "rfec_matrix_wide_blocks.h", CSRC / "rfec_rows_wide_blocks.h"]
 # the receiver units' own headers: only the C host layer includes them
 HOST_HEADERS = HEADERS + [CSRC / f"rfec_rx_{u}.h" for u in ("map", "sim", "pool", "plane", "dev")]
 

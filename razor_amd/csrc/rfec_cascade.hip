@@ -12,6 +12,8 @@
 // (k_decode_cascade and cascade_dense_tail).  The batch kernels' code is sensitive to the form of such sharing,
 // not only to its content: DESIGN 7.13 lists the forms that changed it, and tools/kernel_compare.py is the check.
 #include "rfec_row_blocks.h" // (the row sections of k_decode_shapes_indexed: rfec_fused.hip's bodies)
+#include "rfec_matrix_wide_blocks.h" // (the wide sections of k_decode_window_indexed: rfec_matrix_wide.hip's bodies
+#include "rfec_rows_wide_blocks.h"   //  and rfec_rows_wide.hip's)
 
 namespace {
 
@@ -1010,6 +1012,180 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                            S.divCol[col - 2u], pb)
 }
 
+// The sections of a window of ANY of the planner's shapes in one launch (rfec_recover_indexed_window_out):
+// k_decode_shapes_indexed's scheme -- every section the grid its own call would get, the grids end to end in whole
+// rounds of 8, a block finds its section in the prefix of first blocks and builds the family's argument struct in
+// registers -- over four families: (1) a full matrix of k = 6..16 and (2) a row layout of rows of <= 4 with k <= 64,
+// the compiled bodies as above; (3) a full matrix of k = 17..128, k_decode_matrix_wide's bodies (one checker lane
+// per group); (4) any other row layout, k_decode_rows_wide's.  A wide section keeps its own table pitch (k + n_lines
+// map words, n_lines meta records per group: the bodies take NL from the section, not from ceil(k / col)).
+//
+// The outputs of a section are the call's four arrays from the section's first output row on: the offset goes into
+// the four output BASES of the family's struct, and every body forms its addresses from those bases -- the checker's
+// read-back of the record of a member recovered earlier (cascade_check's and wide_check_block's `ob`) and the
+// replay's slot0 (matrix_payload_block, wide_payload_block) included -- so a cascade's intermediates stay inside
+// the group's own out slots in any section.
+//
+// A section's entry holds what a run-time shape needs beyond ShapeSec: col in 8 bits, its FastDiv, and for a wide
+// matrix the row lines and column 0's member mask.
+struct WinSec {
+    const uint32_t* src_of;
+    const uint32_t* hdr_dw;
+    const uint64_t* present;
+    const uint32_t* meta_dw;
+    const uint16_t* fsize;
+    const uint64_t* parity_present;
+    uint32_t groups, first_row; // rows decoded; the first of its output rows
+    uint32_t shape;             // k | col << 8 | n_lines << 16 | log2 of the header lanes per group << 24 | family << 28
+    uint32_t every;             // payload rounds per header round (Rounds8)
+    FastDiv divCol;             // col
+    uint32_t nr;                // family 3: the row lines (then n_lines - nr column lines)
+    uint64_t col0[2];           // family 3: column 0's member mask
+};
+static_assert(sizeof(WinSec) == 96, "the argument block's budget per section");
+
+struct WindowArgs {
+    WinSec sec[RFEC_RECOVER_MAX_SHAPES];           // the sections with groups, in order
+    uint32_t first_block[RFEC_RECOVER_MAX_SHAPES]; // of each, a multiple of 8
+    uint32_t n;
+    const v4u* rows;
+    uint32_t last, has_rows; // n_rows - 1 (0: none); n_rows != 0 (else no payload lanes)
+    uint64_t* recovered;
+    v4u* out_sh;
+    uint32_t* out_hdr_dw;
+    uint8_t* out_index;
+    uint32_t E, C, cd, capacity;
+    FastDiv divC, divQC; // cd, E * cd
+};
+static_assert(sizeof(WindowArgs) <= 4096, "one argument block");
+
+// (shapes_matrix_block's statements, a copy of this kernel's own: as a second caller of that function this kernel
+// changed k_decode_shapes_indexed's code in the LDS fill)
+template <int K, int COL>
+__device__ __forceinline__ void window_matrix_block(const CascArgs& A, rfec_kmask& sM, bool checker, uint32_t hb,
+                                                    uint32_t pb, const v4u* rows, uint32_t last,
+                                                    const uint32_t* __restrict__ src_of)
+{
+    using LL = MatLines<K, COL>;
+    if (checker) {
+        if (threadIdx.x == 0) {
+            sM.plan.k = K;
+            sM.plan.n_lines = LL::NL;
+        }
+        if (threadIdx.x < (uint32_t)LL::NL) { // (what the serial peel reads: KArgLines)
+            reinterpret_cast<uint32_t*>(sM.plan.line)[threadIdx.x] = LL{}.rec(threadIdx.x);
+            sM.mask[threadIdx.x][0] = LL{}.mask(threadIdx.x);
+            sM.mask[threadIdx.x][1] = 0;
+        }
+        __syncthreads();
+        cascade_check_block<uint32_t, false>(A, sM, LL{}, BatchHdrs{A, sM.plan}, hb);
+    } else {
+        matrix_payload_block<K, COL>(A, BatchHdrs{A, sM.plan}, PoolRows{rows, src_of, K, last, A.C}, pb);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_decode_window_indexed(WindowArgs S)
+{
+    __shared__ rfec_kmask sM;
+    uint32_t p = 0;
+    for (uint32_t q = 1; q < S.n; ++q) // (uniform: scalar loads and compares)
+        p = blockIdx.x >= S.first_block[q] ? q : p;
+    const WinSec& T = S.sec[p];
+    const uint32_t rb = blockIdx.x - S.first_block[p];
+    const uint32_t G = T.groups, K = T.shape & 0xffu, col = (T.shape >> 8) & 0xffu, NL = (T.shape >> 16) & 0xffu;
+    const uint32_t lg = (T.shape >> 24) & 15u, family = T.shape >> 28;
+    // the section's grid, as its own call lays it out (rounds_of_8): G << lg < 2^32 and total < 2^31, host-checked
+    const uint32_t total = S.has_rows ? G * S.E * S.cd : 0u, hl = G << lg;
+    const uint32_t n_hdr = (hl >> 8) + ((hl & 255u) != 0), npay8 = (((total + 255u) >> 8) + 7u) & ~7u;
+    uint32_t hb = 0, pb = 0;
+    const bool header = header_block_xcd_at(rb, (n_hdr + 7u) >> 3, T.every, npay8, &hb, &pb);
+    if (header && hb >= n_hdr) // (the round's blocks past the section's last header lane)
+        return;
+    const size_t o = T.first_row;
+    if (family == 1) { // a full matrix of k = 6..16
+        CascArgs A = {}; // (no shards, no parity, no workspace: rfec_launch_recover_indexed_matrix's)
+        A.hdr_dw = const_cast<uint32_t*>(T.hdr_dw);
+        A.meta_dw = T.meta_dw, A.fsize = T.fsize, A.present = T.present, A.parity_present = T.parity_present;
+        A.recovered = S.recovered + 2 * o;
+        A.out_sh = S.out_sh + o * S.E * S.C;
+        A.out_hdr_dw = S.out_hdr_dw + o * S.E * 5;
+        A.out_index = S.out_index + o * S.E;
+        A.E = A.Q = S.E, A.groups = G, A.total = total, A.C = S.C, A.capacity = S.capacity;
+        A.divC = S.divC, A.divQC = S.divQC;
+#define RFEC_MW(KK, CC)                                                                                           \
+    case KK: window_matrix_block<KK, CC>(A, sM, header, hb, pb, S.rows, S.last, T.src_of); break;
+        switch (K) {
+            RFEC_MATRIX_SHAPES(RFEC_MW)
+        default: break;
+        }
+#undef RFEC_MW
+        return;
+    }
+    if (family == 3) { // a full matrix of k = 17..128: k and col at run time, one checker lane per group
+        WideArgs A = {};
+        A.rows = S.rows, A.src_of = T.src_of, A.hdr_dw = T.hdr_dw, A.meta_dw = T.meta_dw, A.fsize = T.fsize;
+        A.present = T.present, A.parity_present = T.parity_present;
+        A.recovered = S.recovered + 2 * o;
+        A.out_sh = S.out_sh + o * S.E * S.C;
+        A.out_hdr_dw = S.out_hdr_dw + o * S.E * 5;
+        A.out_index = S.out_index + o * S.E;
+        A.E = S.E, A.groups = G, A.total = total, A.C = S.C, A.capacity = S.capacity, A.last = S.last;
+        A.K = K, A.COL = col, A.NR = T.nr, A.NL = NL;
+        A.col0[0] = T.col0[0], A.col0[1] = T.col0[1];
+        A.divC = S.divC, A.divQC = S.divQC, A.divCol = T.divCol;
+        if (header)
+            wide_check_block(A, hb);
+        else
+            wide_payload_block(A, pb);
+        return;
+    }
+    if (family == 4) { // a row layout of any width: k, col and the lines at run time
+        RowsWideArgs A = {};
+        A.rows = S.rows, A.src_of = T.src_of, A.hdr_dw = T.hdr_dw, A.meta_dw = T.meta_dw, A.fsize = T.fsize;
+        A.present = T.present, A.parity_present = T.parity_present;
+        A.recovered = S.recovered + 2 * o;
+        A.out_sh = S.out_sh + o * S.E * S.C;
+        A.out_hdr_dw = S.out_hdr_dw + o * S.E * 5;
+        A.out_index = S.out_index + o * S.E;
+        A.E = S.E, A.groups = G, A.total = total, A.C = S.C, A.capacity = S.capacity, A.last = S.last;
+        A.K = K, A.COL = col, A.NL = NL, A.lg = lg, A.n_hdr = n_hdr;
+        A.divC = S.divC, A.divQC = S.divQC, A.divCol = T.divCol;
+        if (header)
+            rows_wide_header_block(A, hb);
+        else
+            rows_wide_payload_block(A, pb);
+        return;
+    }
+    // family 2, a row layout of rows of <= 4 with k <= 64: k and col at run time, the masks from (k, col)
+    PeelArgs B = {};
+    B.hdr = reinterpret_cast<rfec_hdr*>(const_cast<uint32_t*>(T.hdr_dw)); // dense output: hdr is only read
+    B.present = T.present;
+    B.meta = reinterpret_cast<const rfec_hdr*>(T.meta_dw);
+    B.fsize = T.fsize, B.parity_present = T.parity_present;
+    B.recovered = S.recovered + 2 * o;
+    B.groups = G, B.capacity = S.capacity, B.gpb = 1, B.nlp_log2 = lg;
+    B.out_hdr = reinterpret_cast<rfec_hdr*>(S.out_hdr_dw + o * S.E * 5);
+    B.out_index = S.out_index + o * S.E;
+    B.out_per_group = S.E;
+    if (header) {
+        if (threadIdx.x == 0) {
+            sM.plan.k = (uint16_t)K;
+            sM.plan.n_lines = (uint8_t)NL;
+        }
+        if (threadIdx.x < NL) { // row l: members l col .. of the k
+            const uint32_t first = threadIdx.x * col, cnt = min(col, K - first);
+            reinterpret_cast<uint32_t*>(sM.plan.line)[threadIdx.x] = first | 1u << 8 | cnt << 16;
+            sM.mask[threadIdx.x][0] = ((1ull << cnt) - 1ull) << first;
+            sM.mask[threadIdx.x][1] = 0;
+        }
+        __syncthreads();
+        [[clang::always_inline]] line_headers(B, sM, hb); // (a call would put B on the stack: scratch)
+        return;
+    }
+    const DenseOut D = {S.out_sh + o * S.E * S.C, S.E};
+    RFEC_ROWS_INDEXED_LANE(0, 4, S.rows, S.last, T.src_of, total, S.C, S.divC, S.divQC, B, D, K, col, T.divCol, pb)
+}
+
 // The batch layout -> packed matrix records (rfec_pack_erasures_matrix): one
 // lane per (group, 16-byte chunk of the record), so every byte of a record --
 // masks, slots, zeros and padding -- leaves in whole 16-byte stores (slots
@@ -1312,6 +1488,115 @@ int rfec_launch_recover_indexed_shapes(const rfec_kplan* plans, uint32_t n_plans
         S.divCol[c - 2] = make_fastdiv(c);
     rfec_set_indexed_path(4u | S.n << 8);
     RFEC_LAUNCH(k_decode_shapes_indexed, dim3((uint32_t)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+                S);
+    return (int)hipGetLastError();
+}
+
+// The family of a section of k_decode_window_indexed, the first predicate that holds: 1 the compiled full matrix
+// (k = 6..16), 2 the compiled row layout (rows of <= 4, k <= 64), 3 the planner's full matrix of k = 17..128 in rows
+// of rfec_num_packets' col (rfec_recover_indexed_matrix_wide.c's wide_col and its launcher's bounds), 4 any other
+// row layout (rfec_rows_wide_col and its launcher's bounds); 0: none.
+int rfec_recover_window_family(const rfec_kplan* P)
+{
+    if (rfec_packed_matrix_col(P))
+        return 1;
+    if (rfec_rows_indexed_col(P))
+        return 2;
+    uint8_t row = 0, col = 0;
+    if (P->k >= 6 && P->k <= RFEC_MAX_K && rfec_num_packets(P->k, 255, &row, &col) == 1 && col >= 2 && col <= 20 &&
+        P->n_lines <= kWideSteps && rfec_full_matrix(P, col))
+        return 3;
+    if (P->k >= 2 && P->k <= RFEC_MAX_K && P->n_lines <= RFEC_MAX_LINES && rfec_rows_wide_col(P))
+        return 4;
+    return 0;
+}
+
+// A section's part of k_decode_window_indexed's grid, the one its own call takes: header (or checker) lanes per
+// group 4 (family 1), 2^rfec_header_lanes_log2(n_lines) (families 2 and 4) or 1 (family 3); with n_rows == 0 the
+// header rounds alone.
+static int window_section_grid(const rfec_kplan* P, uint32_t groups, uint32_t E, uint32_t cd, uint32_t n_rows,
+                               uint32_t* lg, Rounds8* g)
+{
+    const int family = rfec_recover_window_family(P);
+    if (!family)
+        return 0;
+    *lg = family == 1 ? rfec_ceil_log2(kCheckLanes) : family == 3 ? 0u : rfec_header_lanes_log2(P->n_lines);
+    *g = rounds_of_8(blocks_for((uint64_t)groups << *lg), blocks_for(n_rows ? (uint64_t)groups * E * cd : 0));
+    return family;
+}
+
+uint32_t rfec_recover_window_blocks(const rfec_kplan* P, uint32_t groups, uint32_t per_group, uint32_t cd,
+                                    uint32_t n_rows)
+{
+    uint32_t lg;
+    Rounds8 g;
+    return window_section_grid(P, groups, per_group, cd, n_rows, &lg, &g) ? g.grid : 0u;
+}
+
+// rfec_recover_indexed_window_out (rfec_recover_indexed_window.c): one launch of k_decode_window_indexed over the
+// sections with groups, no workspace.
+int rfec_launch_recover_indexed_window(const rfec_kplan* plans, uint32_t n_plans, const rfec_regroup_section* sections,
+                                       const uint32_t* groups, uint32_t stride, uint32_t capacity, const uint8_t* rows,
+                                       uint32_t n_rows, uint64_t* recovered, const rfec_dense_out* out, void* stream)
+{
+    const uint32_t cd = capacity ? (capacity + 15) / 16 : 1, E = out ? out->per_group : 0;
+    if (!plans || !sections || !n_plans || n_plans > RFEC_RECOVER_MAX_SHAPES || !stride || stride % 16 ||
+        capacity > stride || !E)
+        return (int)hipErrorInvalidValue;
+    WindowArgs S = {};
+    uint64_t blocks = 0, first_row = 0;
+    for (uint32_t p = 0; p < n_plans; ++p) {
+        const rfec_kplan* P = plans + p;
+        const uint32_t G = groups ? groups[p] : sections[p].cap;
+        if (!G)
+            continue;
+        uint32_t lg;
+        Rounds8 g;
+        const int family = window_section_grid(P, G, E, cd, n_rows, &lg, &g);
+        if (!family || E > P->k || (uint64_t)G * E * cd >= (1ull << 31) || ((uint64_t)G << lg) >= (1ull << 32))
+            return (int)hipErrorInvalidValue;
+        const rfec_regroup_section& s = sections[p];
+        WinSec& T = S.sec[S.n];
+        T.src_of = s.src_of, T.hdr_dw = reinterpret_cast<const uint32_t*>(s.hdr), T.present = s.present;
+        T.meta_dw = reinterpret_cast<const uint32_t*>(s.meta), T.fsize = s.fec_size;
+        T.parity_present = s.parity_present;
+        T.groups = G, T.first_row = (uint32_t)first_row, T.every = g.every;
+        uint32_t col = 0;
+        if (family == 1) {
+            col = (uint32_t)rfec_packed_matrix_col(P);
+        } else if (family == 2) {
+            col = (uint32_t)rfec_rows_indexed_col(P);
+        } else if (family == 3) {
+            uint8_t row = 0, c = 0;
+            rfec_num_packets(P->k, 255, &row, &c);
+            col = c;
+            const uint32_t R = (P->k + col - 1) / col;
+            T.nr = P->k - (R - 1) * col >= 2 ? R : R - 1; // a last row of one member has no line
+            for (uint32_t i = 0; i < P->k; i += col)
+                T.col0[i >> 6] |= 1ull << (i & 63u);
+        } else {
+            col = (uint32_t)rfec_rows_wide_col(P);
+        }
+        T.divCol = make_fastdiv(col);
+        T.shape = P->k | col << 8 | (uint32_t)P->n_lines << 16 | lg << 24 | (uint32_t)family << 28;
+        S.first_block[S.n++] = (uint32_t)blocks;
+        blocks += g.grid;
+        first_row += G;
+        if (blocks >= (1ull << 31) || first_row >= (1ull << 32))
+            return (int)hipErrorInvalidValue;
+    }
+    if (!S.n)
+        return (int)hipSuccess;
+    S.rows = reinterpret_cast<const v4u*>(rows);
+    S.last = n_rows ? n_rows - 1 : 0u, S.has_rows = n_rows != 0;
+    S.recovered = recovered;
+    S.out_sh = reinterpret_cast<v4u*>(out->shards);
+    S.out_hdr_dw = reinterpret_cast<uint32_t*>(out->hdr);
+    S.out_index = out->index;
+    S.E = E, S.C = stride / 16, S.cd = cd, S.capacity = capacity;
+    S.divC = make_fastdiv(cd), S.divQC = make_fastdiv(E * cd);
+    rfec_set_indexed_path(8u | S.n << 8);
+    RFEC_LAUNCH(k_decode_window_indexed, dim3((uint32_t)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
                 S);
     return (int)hipGetLastError();
 }

@@ -263,6 +263,25 @@ int rfec_launch_recover_indexed_shapes(const rfec_kplan* plans, uint32_t n_plans
  * 16-byte chunks of work per slot); 0 for a plan of neither shape */
 uint32_t rfec_recover_shapes_blocks(const rfec_kplan* P, uint32_t groups, uint32_t per_group, uint32_t cd,
                                     uint32_t n_rows);
+/* rfec_recover_indexed_window_out (rfec_recover_indexed_window.c, kernel in rfec_cascade.hip): the same sections in
+ * one launch of k_decode_window_indexed, for any of the planner's shapes.  rfec_recover_window_family is the rule, the
+ * first predicate that holds: 1 rfec_packed_matrix_col != 0 (as rfec_launch_recover_indexed_matrix decodes it),
+ * 2 rfec_rows_indexed_col != 0 (as rfec_launch_recover_indexed's one launch), 3 the planner's full matrix of
+ * k = 17..128 (rfec_num_packets' col in [2, 20], rfec_full_matrix, at most 23 lines: as
+ * rfec_launch_recover_indexed_matrix_wide), 4 rfec_rows_wide_col != 0 with k >= 2 (as
+ * rfec_launch_recover_indexed_rows_wide); 0: refused.  The caller has checked what
+ * rfec_launch_recover_indexed_shapes' has, with every section's family and that family's bounds;
+ * hipErrorInvalidValue otherwise.  All groups[p] == 0: no launch.  No flags: rfec_set_tuning does not reach this
+ * call. */
+int rfec_recover_window_family(const rfec_kplan* P);
+int rfec_launch_recover_indexed_window(const rfec_kplan* plans, uint32_t n_plans, const rfec_regroup_section* sections,
+                                       const uint32_t* groups, uint32_t stride, uint32_t capacity, const uint8_t* rows,
+                                       uint32_t n_rows, uint64_t* recovered, const rfec_dense_out* out, void* stream);
+/* the blocks of one section's part of that launch's grid, a multiple of 8: the grid its family's own call would take
+ * (header or checker lanes per group: 4, 2^rfec_header_lanes_log2(n_lines), 1, 2^rfec_header_lanes_log2(n_lines));
+ * 0 for a refused plan */
+uint32_t rfec_recover_window_blocks(const rfec_kplan* P, uint32_t groups, uint32_t per_group, uint32_t cd,
+                                    uint32_t n_rows);
 /* rfec_recover_deliver (rfec_recover_deliver.c, kernels in rfec_deliver.hip): the outputs of
  * rfec_launch_recover_indexed_shapes as a dense list in window order, in three launches on `stream` (k_deliver_count,
  * k_deliver_totals, k_deliver), two when groups <= 256 (one block counts the window and writes the totals).  first:
@@ -277,8 +296,8 @@ int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n
                                 uint8_t* seg_payload, uint32_t* first_of, uint32_t* n_out, void* workspace,
                                 void* stream);
 /* Which kernels the calling thread's last rfec_launch_recover_indexed, rfec_launch_recover_indexed_matrix,
- * rfec_launch_recover_indexed_matrix_wide, rfec_launch_recover_indexed_rows_wide, rfec_launch_recover_indexed_shapes
- * or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
+ * rfec_launch_recover_indexed_matrix_wide, rfec_launch_recover_indexed_rows_wide, rfec_launch_recover_indexed_shapes,
+ * rfec_launch_recover_indexed_window or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
  * from rfec_last_path, whose kinds are a closed table): 0 none yet,
  * 1 | K << 8 one launch of k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8
  * k_peel_lds + k_recover_indexed<MAXC, ...> (MAXC = 4, 8), 3 | K << 8 one launch of k_decode_matrix_indexed<K, col>
@@ -287,7 +306,8 @@ int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n
  * rfec_launch_recover_deliver (k_deliver_count, k_deliver_totals for a window of more than 256 groups, k_deliver),
  * 6 | k << 8 one launch of k_decode_matrix_wide (k = 6..128; rfec_launch_recover_indexed_matrix_wide only),
  * 7 | k << 8 | col << 16 one launch of k_decode_rows_wide (k = 2..128 in rows of col = 2..128;
- * rfec_launch_recover_indexed_rows_wide only). */
+ * rfec_launch_recover_indexed_rows_wide only), 8 | n << 8 one launch of k_decode_window_indexed over n sections
+ * with groups (rfec_launch_recover_indexed_window only). */
 uint32_t rfec_indexed_last_path(void);
 /* Which kernel the calling thread's last wire-codec launch (rfec_wire.hip: the rfec_launch_wire_* shims) took, and on
  * how many blocks: kernel id | grid blocks << 8, 0 before the first (host-side, thread-local, for tests; apart from

@@ -285,6 +285,9 @@ _SIGS = {
     "rfec_recover_indexed_shapes_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
                                                   C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_uint32, _P,
                                                   C.c_uint32, _P, _P, _P, _P]),
+    "rfec_recover_indexed_window_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
+                                                  C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, _P, C.c_uint32, _P,
+                                                  C.c_uint32, _P, _P, _P, _P]),
     "rfec_recover_deliver_workspace_size": (C.c_size_t, [C.c_uint32]),
     "rfec_recover_deliver": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
                                        C.POINTER(C.c_uint32), C.c_uint32, C.c_uint16, _P, _P, C.c_uint32, C.c_uint32,
@@ -640,6 +643,23 @@ class Native:
         self._check(self.lib.rfec_recover_indexed_shapes_out(pa, len(plans), sa, ga, stride, capacity, rows, n_rows,
                                                              recovered, per_group, out_shards, out_hdr, out_index,
                                                              stream), "rfec_recover_indexed_shapes_out")
+
+    def recover_indexed_window_out(self, plans, sections, groups, stride, capacity, rows, n_rows, recovered,
+                                   per_group, out_shards, out_hdr, out_index, stream=None):
+        """rfec_recover_indexed_window_out: recover_indexed_shapes_out for a window of any of the planner's shapes
+        (strip-mode plans and full matrices up to k = 128 beside the compiled shapes), one launch; the same
+        arguments and output numbering, so recover_deliver takes its outputs unchanged."""
+        if len(plans) != len(sections):
+            raise ValueError("one section per plan")
+        if groups is not None and len(groups) != len(plans):
+            raise ValueError("one group count per plan")
+        pa = (rfec_plan * max(len(plans), 1))(*(as_plan(p) for p in plans))
+        sa = (rfec_regroup_section * max(len(sections), 1))(
+            *(s if isinstance(s, rfec_regroup_section) else rfec_regroup_section(**s) for s in sections))
+        ga = None if groups is None else (C.c_uint32 * max(len(groups), 1))(*(int(g) for g in groups))
+        self._check(self.lib.rfec_recover_indexed_window_out(pa, len(plans), sa, ga, stride, capacity, rows, n_rows,
+                                                             recovered, per_group, out_shards, out_hdr, out_index,
+                                                             stream), "rfec_recover_indexed_window_out")
 
     def recover_deliver_workspace_size(self, window_groups) -> int:
         return int(self.lib.rfec_recover_deliver_workspace_size(window_groups))
