@@ -401,7 +401,7 @@ int rfec_host_recover_groups(const rfec_plan* plan, uint32_t groups, sim_segment
 
 /* Kernel timing for benches: the next kernel this thread launches through the
  * batched API (rfec_encode_batch, rfec_recover_batch[_out], rfec_zero_tails,
- * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_matrix_wide_out, rfec_recover_indexed_rows_wide_out, rfec_recover_indexed_shapes_out, rfec_recover_deliver) records its own start / stop on these hipEvent_t (either may be NULL), via
+ * rfec_wire_frame_fec / _seg, rfec_wire_encode_fec, rfec_wire_encode_send, rfec_wire_encode_send_shapes, rfec_wire_parse, rfec_wire_regroup[_index], rfec_recover_indexed_out, rfec_recover_indexed_matrix_out, rfec_recover_indexed_matrix_wide_out, rfec_recover_indexed_rows_wide_out, rfec_recover_indexed_shapes_out, rfec_recover_indexed_window_out, rfec_recover_indexed_window_each_out, rfec_recover_deliver, rfec_recover_deliver_each) records its own start / stop on these hipEvent_t (either may be NULL), via
  * hipExtLaunchKernel; the setting is consumed by that launch.
  * rfec_timing_launches: kernels launched by this thread since the last
  * rfec_timing_events (a call that launched more than one kernel timed only
@@ -1171,6 +1171,72 @@ int rfec_recover_indexed_window_out(const rfec_plan* plans, uint32_t n_plans,
                                     uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index,
                                     void* stream);
 
+/*
+ * rfec_recover_indexed_window_out with an out-slot count per section: the same
+ * arguments with per_group a host array [n_plans], so that a window's small
+ * groups do not bound what its large ones deliver.  With one per_group for the
+ * call a window of 1 x 3 P-frame groups and a 100-segment I-frame gets 3 out
+ * slots per group; here the I-frame's section takes per_group[p] = 10 (or up
+ * to 100) beside the P-frames' 3.  The families, the NULL rules and what a
+ * section with groups[p] == 0 may hold are rfec_recover_indexed_window_out's.
+ *
+ * Output numbering ("the ragged numbering"): first[p] is the sum of groups[q]
+ * over q < p and slot_first[p] the sum of groups[q] * per_group[q] over q < p,
+ * groups[p] = sections[p].cap when groups is NULL.  Row c of section p is
+ * output row o = first[p] + c; recovered is indexed by o.  out_index, out_hdr
+ * and out_shards are indexed by slot: out slot e < per_group[p] of that row is
+ * slot slot_first[p] + c * per_group[p] + e.  Section p's rows have
+ * per_group[p] slots each and the sections' slots are packed end to end:
+ * S = slot_first[n_plans] = rfec_recover_window_slots(...) slots in all, so
+ * out_index holds S bytes, out_hdr S records and out_shards S * stride bytes.
+ *
+ * Results: for every p with groups[p] > 0, rows [first[p], first[p] +
+ * groups[p]) of recovered and slots [slot_first[p], slot_first[p + 1]) of
+ * out_index, out_hdr and out_shards hold byte for byte what its family's
+ * single-shape call writes into arrays of its own for (&plans[p], groups[p],
+ * stride, capacity, rows, n_rows, section p's tables, per_group[p]): recovered,
+ * out_index, out_hdr, and out_shards over [0, 16 CD) of every slot whose
+ * out_index is not 0xFF.  "Slot tails": bytes [16 CD, stride) of every out slot
+ * are not written; the payload of a 0xFF slot is unspecified; every input is
+ * untouched.  Everything else rfec_recover_indexed_window_out says of its
+ * results holds.  With every per_group[p] equal to E the outputs are byte for
+ * byte those of rfec_recover_indexed_window_out(..., E, ...).
+ *
+ * Checked before any runtime call (RFEC_EINVAL), in
+ * rfec_recover_indexed_window_out's order with per_group where it stands
+ * there: plans not NULL, n_plans in [1, RFEC_RECOVER_MAX_SHAPES], sections not
+ * NULL, each plan and, with groups[p] > 0, its family; stride a positive
+ * multiple of 16, capacity <= stride; per_group not NULL and, for each section
+ * with groups[p] > 0, per_group[p] in [1, plans[p].k] (rfec_last_error names
+ * per_group[p]; per_group[p] of a section with groups[p] == 0 is not read for
+ * range and may be anything, 0 included); per section groups[p] <= cap,
+ * groups[p] * per_group[p] * CD < 2^31 and the header lanes' bound of its
+ * family; the launch's blocks < 2^31, its output rows < 2^32 and S * CD <
+ * 2^31.  All groups[p] == 0 touches nothing: every other pointer may be NULL.
+ * Then NULL pointers and alignment as rfec_recover_indexed_window_out.  The
+ * call uses no workspace, allocates nothing, copies nothing from the host (the
+ * sections and their per_group travel as kernel arguments), does not
+ * synchronise and makes exactly one launch on `stream`; no workgroup waits on
+ * another.
+ */
+int rfec_recover_indexed_window_each_out(const rfec_plan* plans, uint32_t n_plans,
+                                         const rfec_regroup_section* sections,
+                                         const uint32_t* groups, /* host [n_plans], or NULL: sections[p].cap */
+                                         uint32_t stride, uint32_t capacity,
+                                         const uint8_t* rows, uint32_t n_rows,
+                                         uint64_t* recovered,
+                                         const uint32_t* per_group, /* host [n_plans] */
+                                         uint8_t* out_shards, rfec_hdr* out_hdr, uint8_t* out_index,
+                                         void* stream);
+
+/* S of the ragged numbering: the sum over p of groups[p] * per_group[p]
+ * (groups[p] = sections[p].cap when groups is NULL; per_group[p] of a section
+ * with groups[p] == 0 is not read), the out slots the three slot arrays of
+ * rfec_recover_indexed_window_each_out hold.  Host arithmetic only: no device,
+ * no checks; 0 when per_group is NULL, or groups and sections both. */
+uint64_t rfec_recover_window_slots(const rfec_regroup_section* sections, uint32_t n_plans,
+                                   const uint32_t* groups, const uint32_t* per_group);
+
 /* One delivered segment, as every call that hands recovered segments back
  * writes it (rfec_recover_deliver below; rfec_rx_recover, the rx session). */
 typedef struct {
@@ -1259,6 +1325,47 @@ int rfec_recover_deliver(const rfec_plan* plans, uint32_t n_plans,            /*
                          uint32_t* first_of,                                  /* device [G + 1] */
                          uint32_t* n_out,                                     /* device [1] */
                          void* workspace, void* stream);
+
+/*
+ * rfec_recover_deliver over what rfec_recover_indexed_window_each_out wrote:
+ * the same arguments with per_group the host array [n_plans] given to that
+ * decode, the slot arrays in the ragged numbering (slot_first[p] the sum of
+ * groups[q] * per_group[q] over q < p; out slot e < per_group[p] of row c of
+ * section p is slot slot_first[p] + c * per_group[p] + e).  The rule is
+ * rfec_recover_deliver's except in two places:
+ *  3. Counts.  For a decoded group g with p = shape_of[g] and c = rank_of[g],
+ *     n_g is the number of e < per_group[p] with out_index[slot_first[p] +
+ *     c * per_group[p] + e] != 0xFF.
+ *  5, 6. Order and entries read that slot: out slot e of group g is entry j =
+ *     first_of[g] + the number of e' < e whose slot is not 0xFF, seg[j].hdr is
+ *     out_hdr of the slot and row j of seg_payload over [0, 16 CD) its bytes.
+ * With every per_group[p] equal to E all six outputs are byte for byte those of
+ * rfec_recover_deliver(..., E, ...).  What is written, the tables' consistency,
+ * the workspace (rfec_recover_deliver_workspace_size(G)) and the launches
+ * (three, two when window_groups <= 256) are rfec_recover_deliver's.
+ *
+ * Checked before any runtime call (RFEC_EINVAL), in rfec_recover_deliver's
+ * order with per_group where it stands there: per_group not NULL and
+ * per_group[p] >= 1 for every section with groups[p] > 0 (rfec_last_error
+ * names per_group[p]; not read where groups[p] == 0, nor when sections is NULL
+ * with window_groups == 0); groups[p] <= sections[p].cap; S * CD < 2^31 with
+ * S = slot_first[n_plans], and R < 2^32.  Everything else as
+ * rfec_recover_deliver.
+ */
+int rfec_recover_deliver_each(const rfec_plan* plans, uint32_t n_plans,       /* host */
+                              const rfec_regroup_section* sections,           /* host, of device pointers: group_of is read */
+                              const uint32_t* groups,                         /* host [n_plans] or NULL: sections[p].cap */
+                              uint32_t window_groups, uint16_t fec_id0,
+                              const uint8_t* shape_of, const uint32_t* rank_of, /* device [G], as regroup_shapes wrote them */
+                              uint32_t stride, uint32_t capacity,
+                              const uint32_t* per_group,                      /* host [n_plans] */
+                              const uint8_t* out_shards, const rfec_hdr* out_hdr, /* device: the decode's outputs */
+                              const uint8_t* out_index,
+                              uint32_t max_out,
+                              rfec_rx_seg* seg, uint8_t* seg_payload,         /* device [max_out], [max_out][stride] */
+                              uint32_t* first_of,                             /* device [G + 1] */
+                              uint32_t* n_out,                                /* device [1] */
+                              void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------ */
 /* Sender staging: sim_sender_put (sim_sender.c:306-377) with sim_split_frame */

@@ -45,8 +45,10 @@ HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused"
 # in rfec_matrix_wide.hip; rfec_recover_indexed_rows_wide.c: for a row layout of any width, kernel in
 # rfec_rows_wide.hip) and rfec_recover_indexed_shapes.c (its one-launch form for a window's sections of
 # several shapes; rfec_recover_indexed_window.c: for a window of any of the planner's shapes, the wide kernels' bodies
-# shared through rfec_matrix_wide_blocks.h and rfec_rows_wide_blocks.h) and rfec_recover_deliver.c (that decode's outputs as a list of delivered segments in window order,
-# kernels in rfec_deliver.hip) call launch shims of their own,
+# shared through rfec_matrix_wide_blocks.h and rfec_rows_wide_blocks.h; rfec_recover_indexed_window_each.c: the same
+# with an out-slot count per section) and rfec_recover_deliver.c (that decode's outputs as a list of delivered
+# segments in window order, kernels in rfec_deliver.hip; rfec_recover_deliver_each.c: over the per-section slot
+# counts) call launch shims of their own,
 # so they stay out of HOST_SRC: the CPU builds of the host layer compile exactly HOST_SRC against a stub of the runtime
 HOST_NOHIP_SRC = ["rfec_rx_sim.c", "rfec_rx_pool.c", "rfec_rx_plane.c"]  # no GPU runtime: built and tested alone
 HOST_SRC = ["rfec_host.c", "rfec_dropin.c", "rfec_hostmem.c", "rfec_sender.c", *HOST_NOHIP_SRC, "rfec_rx_dev.c",
@@ -57,7 +59,9 @@ C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packe
                                           CSRC / "rfec_recover_indexed_shapes.c", CSRC / "rfec_recover_deliver.c",
                                           CSRC / "rfec_recover_indexed_matrix_wide.c",
                                           CSRC / "rfec_recover_indexed_rows_wide.c",
-                                          CSRC / "rfec_recover_indexed_window.c"]
+                                          CSRC / "rfec_recover_indexed_window.c",
+                                          CSRC / "rfec_recover_indexed_window_each.c",
+                                          CSRC / "rfec_recover_deliver_each.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h", CSRC / "rfec_device.h", CSRC / "rfec_families.h",

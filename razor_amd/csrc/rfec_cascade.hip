@@ -1186,6 +1186,169 @@ __global__ __launch_bounds__(kBlock) void k_decode_window_indexed(WindowArgs S)
     RFEC_ROWS_INDEXED_LANE(0, 4, S.rows, S.last, T.src_of, total, S.C, S.divC, S.divQC, B, D, K, col, T.divCol, pb)
 }
 
+// k_decode_window_indexed with an out-slot count per section (rfec_recover_indexed_window_each_out): section p's
+// rows have E[p] out slots each and the sections' slots are packed end to end, so `recovered` is still indexed by
+// output row first[p] + c while out_index, out_hdr and out_shards are indexed by slot slot_first[p] + c E[p] + e,
+// slot_first[p] the sum of groups[q] E[q] over q < p.  The same scheme: window_section_grid with the section's own E,
+// the grids end to end in whole rounds of 8.  Every family's struct already carries its own E, total and divQC and
+// every body forms its addresses from the struct's bases and that E (the cascades' read-back included), so the
+// section's entry gains E, its first slot and the FastDiv of E cd, the bases are taken from the first slot instead
+// of first_row E, and the bodies are untouched.
+struct WinSecEach {
+    const uint32_t* src_of;
+    const uint32_t* hdr_dw;
+    const uint64_t* present;
+    const uint32_t* meta_dw;
+    const uint16_t* fsize;
+    const uint64_t* parity_present;
+    uint32_t groups, first_row; // rows decoded; the first of its output rows
+    uint32_t shape;             // as WinSec's
+    uint32_t every;             // payload rounds per header round (Rounds8)
+    FastDiv divCol;             // col
+    uint32_t nr;                // family 3: the row lines (then n_lines - nr column lines)
+    uint32_t E, slot_first;     // out slots per row; the first of its out slots
+    FastDiv divQC;              // E * cd
+    uint64_t col0[2];           // family 3: column 0's member mask
+};
+static_assert(sizeof(WinSecEach) == 120, "the argument block's budget per section");
+
+struct WindowEachArgs {
+    WinSecEach sec[RFEC_RECOVER_MAX_SHAPES];       // the sections with groups, in order
+    uint32_t first_block[RFEC_RECOVER_MAX_SHAPES]; // of each, a multiple of 8
+    uint32_t n;
+    const v4u* rows;
+    uint32_t last, has_rows; // n_rows - 1 (0: none); n_rows != 0 (else no payload lanes)
+    uint64_t* recovered;
+    v4u* out_sh;
+    uint32_t* out_hdr_dw;
+    uint8_t* out_index;
+    uint32_t C, cd, capacity;
+    FastDiv divC; // cd
+};
+static_assert(sizeof(WindowEachArgs) <= 4096, "one argument block");
+
+// (window_matrix_block's statements, a copy of this kernel's own: see there)
+template <int K, int COL>
+__device__ __forceinline__ void window_each_matrix_block(const CascArgs& A, rfec_kmask& sM, bool checker, uint32_t hb,
+                                                         uint32_t pb, const v4u* rows, uint32_t last,
+                                                         const uint32_t* __restrict__ src_of)
+{
+    using LL = MatLines<K, COL>;
+    if (checker) {
+        if (threadIdx.x == 0) {
+            sM.plan.k = K;
+            sM.plan.n_lines = LL::NL;
+        }
+        if (threadIdx.x < (uint32_t)LL::NL) { // (what the serial peel reads: KArgLines)
+            reinterpret_cast<uint32_t*>(sM.plan.line)[threadIdx.x] = LL{}.rec(threadIdx.x);
+            sM.mask[threadIdx.x][0] = LL{}.mask(threadIdx.x);
+            sM.mask[threadIdx.x][1] = 0;
+        }
+        __syncthreads();
+        cascade_check_block<uint32_t, false>(A, sM, LL{}, BatchHdrs{A, sM.plan}, hb);
+    } else {
+        matrix_payload_block<K, COL>(A, BatchHdrs{A, sM.plan}, PoolRows{rows, src_of, K, last, A.C}, pb);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_decode_window_each(WindowEachArgs S)
+{
+    __shared__ rfec_kmask sM;
+    uint32_t p = 0;
+    for (uint32_t q = 1; q < S.n; ++q) // (uniform: scalar loads and compares)
+        p = blockIdx.x >= S.first_block[q] ? q : p;
+    const WinSecEach& T = S.sec[p];
+    const uint32_t rb = blockIdx.x - S.first_block[p];
+    const uint32_t G = T.groups, K = T.shape & 0xffu, col = (T.shape >> 8) & 0xffu, NL = (T.shape >> 16) & 0xffu;
+    const uint32_t lg = (T.shape >> 24) & 15u, family = T.shape >> 28, E = T.E;
+    // the section's grid, as its own call lays it out (rounds_of_8): G << lg < 2^32 and total < 2^31, host-checked
+    const uint32_t total = S.has_rows ? G * E * S.cd : 0u, hl = G << lg;
+    const uint32_t n_hdr = (hl >> 8) + ((hl & 255u) != 0), npay8 = (((total + 255u) >> 8) + 7u) & ~7u;
+    uint32_t hb = 0, pb = 0;
+    const bool header = header_block_xcd_at(rb, (n_hdr + 7u) >> 3, T.every, npay8, &hb, &pb);
+    if (header && hb >= n_hdr) // (the round's blocks past the section's last header lane)
+        return;
+    // the section's four output bases: its first row of `recovered`, its first slot of the three slot arrays
+    const size_t sf = T.slot_first;
+    uint64_t* const recovered = S.recovered + 2 * (size_t)T.first_row;
+    v4u* const out_sh = S.out_sh + sf * S.C;
+    uint32_t* const out_hdr_dw = S.out_hdr_dw + sf * 5;
+    uint8_t* const out_index = S.out_index + sf;
+    if (family == 1) { // a full matrix of k = 6..16
+        CascArgs A = {}; // (no shards, no parity, no workspace: rfec_launch_recover_indexed_matrix's)
+        A.hdr_dw = const_cast<uint32_t*>(T.hdr_dw);
+        A.meta_dw = T.meta_dw, A.fsize = T.fsize, A.present = T.present, A.parity_present = T.parity_present;
+        A.recovered = recovered, A.out_sh = out_sh, A.out_hdr_dw = out_hdr_dw, A.out_index = out_index;
+        A.E = A.Q = E, A.groups = G, A.total = total, A.C = S.C, A.capacity = S.capacity;
+        A.divC = S.divC, A.divQC = T.divQC;
+#define RFEC_ME(KK, CC)                                                                                           \
+    case KK: window_each_matrix_block<KK, CC>(A, sM, header, hb, pb, S.rows, S.last, T.src_of); break;
+        switch (K) {
+            RFEC_MATRIX_SHAPES(RFEC_ME)
+        default: break;
+        }
+#undef RFEC_ME
+        return;
+    }
+    if (family == 3) { // a full matrix of k = 17..128: k and col at run time, one checker lane per group
+        WideArgs A = {};
+        A.rows = S.rows, A.src_of = T.src_of, A.hdr_dw = T.hdr_dw, A.meta_dw = T.meta_dw, A.fsize = T.fsize;
+        A.present = T.present, A.parity_present = T.parity_present;
+        A.recovered = recovered, A.out_sh = out_sh, A.out_hdr_dw = out_hdr_dw, A.out_index = out_index;
+        A.E = E, A.groups = G, A.total = total, A.C = S.C, A.capacity = S.capacity, A.last = S.last;
+        A.K = K, A.COL = col, A.NR = T.nr, A.NL = NL;
+        A.col0[0] = T.col0[0], A.col0[1] = T.col0[1];
+        A.divC = S.divC, A.divQC = T.divQC, A.divCol = T.divCol;
+        if (header)
+            wide_check_block(A, hb);
+        else
+            wide_payload_block(A, pb);
+        return;
+    }
+    if (family == 4) { // a row layout of any width: k, col and the lines at run time
+        RowsWideArgs A = {};
+        A.rows = S.rows, A.src_of = T.src_of, A.hdr_dw = T.hdr_dw, A.meta_dw = T.meta_dw, A.fsize = T.fsize;
+        A.present = T.present, A.parity_present = T.parity_present;
+        A.recovered = recovered, A.out_sh = out_sh, A.out_hdr_dw = out_hdr_dw, A.out_index = out_index;
+        A.E = E, A.groups = G, A.total = total, A.C = S.C, A.capacity = S.capacity, A.last = S.last;
+        A.K = K, A.COL = col, A.NL = NL, A.lg = lg, A.n_hdr = n_hdr;
+        A.divC = S.divC, A.divQC = T.divQC, A.divCol = T.divCol;
+        if (header)
+            rows_wide_header_block(A, hb);
+        else
+            rows_wide_payload_block(A, pb);
+        return;
+    }
+    // family 2, a row layout of rows of <= 4 with k <= 64: k and col at run time, the masks from (k, col)
+    PeelArgs B = {};
+    B.hdr = reinterpret_cast<rfec_hdr*>(const_cast<uint32_t*>(T.hdr_dw)); // dense output: hdr is only read
+    B.present = T.present;
+    B.meta = reinterpret_cast<const rfec_hdr*>(T.meta_dw);
+    B.fsize = T.fsize, B.parity_present = T.parity_present;
+    B.recovered = recovered;
+    B.groups = G, B.capacity = S.capacity, B.gpb = 1, B.nlp_log2 = lg;
+    B.out_hdr = reinterpret_cast<rfec_hdr*>(out_hdr_dw);
+    B.out_index = out_index;
+    B.out_per_group = E;
+    if (header) {
+        if (threadIdx.x == 0) {
+            sM.plan.k = (uint16_t)K;
+            sM.plan.n_lines = (uint8_t)NL;
+        }
+        if (threadIdx.x < NL) { // row l: members l col .. of the k
+            const uint32_t first = threadIdx.x * col, cnt = min(col, K - first);
+            reinterpret_cast<uint32_t*>(sM.plan.line)[threadIdx.x] = first | 1u << 8 | cnt << 16;
+            sM.mask[threadIdx.x][0] = ((1ull << cnt) - 1ull) << first;
+            sM.mask[threadIdx.x][1] = 0;
+        }
+        __syncthreads();
+        [[clang::always_inline]] line_headers(B, sM, hb); // (a call would put B on the stack: scratch)
+        return;
+    }
+    const DenseOut D = {out_sh, E};
+    RFEC_ROWS_INDEXED_LANE(0, 4, S.rows, S.last, T.src_of, total, S.C, S.divC, T.divQC, B, D, K, col, T.divCol, pb)
+}
+
 // The batch layout -> packed matrix records (rfec_pack_erasures_matrix): one
 // lane per (group, 16-byte chunk of the record), so every byte of a record --
 // masks, slots, zeros and padding -- leaves in whole 16-byte stores (slots
@@ -1597,6 +1760,79 @@ int rfec_launch_recover_indexed_window(const rfec_kplan* plans, uint32_t n_plans
     S.divC = make_fastdiv(cd), S.divQC = make_fastdiv(E * cd);
     rfec_set_indexed_path(8u | S.n << 8);
     RFEC_LAUNCH(k_decode_window_indexed, dim3((uint32_t)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
+                S);
+    return (int)hipGetLastError();
+}
+
+// rfec_recover_indexed_window_each_out (rfec_recover_indexed_window_each.c): one launch of k_decode_window_each over
+// the sections with groups, section p with per_group[p] out slots a row, the slots packed end to end; no workspace.
+int rfec_launch_recover_indexed_window_each(const rfec_kplan* plans, uint32_t n_plans,
+                                            const rfec_regroup_section* sections, const uint32_t* groups,
+                                            uint32_t stride, uint32_t capacity, const uint8_t* rows, uint32_t n_rows,
+                                            uint64_t* recovered, const uint32_t* per_group, uint8_t* out_shards,
+                                            rfec_hdr* out_hdr, uint8_t* out_index, void* stream)
+{
+    const uint32_t cd = capacity ? (capacity + 15) / 16 : 1;
+    if (!plans || !sections || !n_plans || n_plans > RFEC_RECOVER_MAX_SHAPES || !stride || stride % 16 ||
+        capacity > stride || !per_group)
+        return (int)hipErrorInvalidValue;
+    WindowEachArgs S = {};
+    uint64_t blocks = 0, first_row = 0, slot_first = 0;
+    for (uint32_t p = 0; p < n_plans; ++p) {
+        const rfec_kplan* P = plans + p;
+        const uint32_t G = groups ? groups[p] : sections[p].cap;
+        if (!G)
+            continue;
+        const uint32_t E = per_group[p];
+        uint32_t lg;
+        Rounds8 g;
+        const int family = E ? window_section_grid(P, G, E, cd, n_rows, &lg, &g) : 0;
+        if (!family || E > P->k || (uint64_t)G * E * cd >= (1ull << 31) || ((uint64_t)G << lg) >= (1ull << 32))
+            return (int)hipErrorInvalidValue;
+        const rfec_regroup_section& s = sections[p];
+        WinSecEach& T = S.sec[S.n];
+        T.src_of = s.src_of, T.hdr_dw = reinterpret_cast<const uint32_t*>(s.hdr), T.present = s.present;
+        T.meta_dw = reinterpret_cast<const uint32_t*>(s.meta), T.fsize = s.fec_size;
+        T.parity_present = s.parity_present;
+        T.groups = G, T.first_row = (uint32_t)first_row, T.every = g.every;
+        T.E = E, T.slot_first = (uint32_t)slot_first, T.divQC = make_fastdiv(E * cd);
+        uint32_t col = 0;
+        if (family == 1) {
+            col = (uint32_t)rfec_packed_matrix_col(P);
+        } else if (family == 2) {
+            col = (uint32_t)rfec_rows_indexed_col(P);
+        } else if (family == 3) {
+            uint8_t row = 0, c = 0;
+            rfec_num_packets(P->k, 255, &row, &c);
+            col = c;
+            const uint32_t R = (P->k + col - 1) / col;
+            T.nr = P->k - (R - 1) * col >= 2 ? R : R - 1; // a last row of one member has no line
+            for (uint32_t i = 0; i < P->k; i += col)
+                T.col0[i >> 6] |= 1ull << (i & 63u);
+        } else {
+            col = (uint32_t)rfec_rows_wide_col(P);
+        }
+        T.divCol = make_fastdiv(col);
+        T.shape = P->k | col << 8 | (uint32_t)P->n_lines << 16 | lg << 24 | (uint32_t)family << 28;
+        S.first_block[S.n++] = (uint32_t)blocks;
+        blocks += g.grid;
+        first_row += G;
+        slot_first += (uint64_t)G * E;
+        if (blocks >= (1ull << 31) || first_row >= (1ull << 32) || slot_first * cd >= (1ull << 31))
+            return (int)hipErrorInvalidValue;
+    }
+    if (!S.n)
+        return (int)hipSuccess;
+    S.rows = reinterpret_cast<const v4u*>(rows);
+    S.last = n_rows ? n_rows - 1 : 0u, S.has_rows = n_rows != 0;
+    S.recovered = recovered;
+    S.out_sh = reinterpret_cast<v4u*>(out_shards);
+    S.out_hdr_dw = reinterpret_cast<uint32_t*>(out_hdr);
+    S.out_index = out_index;
+    S.C = stride / 16, S.cd = cd, S.capacity = capacity;
+    S.divC = make_fastdiv(cd);
+    rfec_set_indexed_path(9u | S.n << 8);
+    RFEC_LAUNCH(k_decode_window_each, dim3((uint32_t)blocks), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
                 S);
     return (int)hipGetLastError();
 }

@@ -213,6 +213,108 @@ __global__ __launch_bounds__(kBlock) void k_deliver(const Sect S, const Deliver 
         st16(D.pay + (size_t)j * D.C + chunk, ld16(D.out_sh + (size_t)s * D.C + chunk));
 }
 
+// rfec_recover_deliver_each: the same three launches over the outputs of rfec_recover_indexed_window_each_out, whose
+// section p has E[p] out slots a row and the sections' slots packed end to end: out slot e of row c of section p is
+// slot slot_first[p] + c E[p] + e, slot_first[p] the sum of groups[q] E[q] over q < p.  k_deliver_totals is the one
+// above.  A slot lane finds its section by wave-uniform compares over slot_first[] and its (row, e) by the section's
+// own FastDiv, read through scalar loads inside for_plan (three words and a v_mul_hi_u32; the compiler's division by
+// a run-time E is a reciprocal sequence of some twenty VALU instructions per lane).
+struct SectEach {
+    const uint32_t* group_of[kShapes];
+    uint32_t first[kShapes + 1];      // rows
+    uint32_t slot_first[kShapes + 1]; // out slots
+    uint32_t E[kShapes];              // out slots a row (a section without rows: 1)
+    FastDiv divE[kShapes];
+    uint32_t n_plans;
+};
+static_assert(sizeof(SectEach) + sizeof(Deliver) <= 4096 && sizeof(SectEach) + 16 * sizeof(void*) <= 4096,
+              "the argument block (k_deliver_each; k_deliver_count_each)");
+
+__global__ __launch_bounds__(kBlock) void k_deliver_count_each(const SectEach S, uint32_t G,
+                                                               const uint8_t* __restrict__ shape_of,
+                                                               const uint32_t* __restrict__ rank_of,
+                                                               const uint8_t* __restrict__ out_index,
+                                                               uint32_t* __restrict__ local, uint32_t* __restrict__ blk,
+                                                               uint32_t* __restrict__ first_of,
+                                                               uint32_t* __restrict__ n_out, uint32_t single)
+{
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t n = 0;
+    if (g < G) {
+        const uint32_t p = shape_of[g], c = rank_of[g];
+        if (p < S.n_plans)
+            for_plan(p, [&](uint32_t p0) {
+                if (c >= S.first[p0 + 1] - S.first[p0])
+                    return; // a rank past the rows decoded (RFEC_REGROUP_NONE among them)
+                const uint32_t E = S.E[p0];
+                const uint8_t* ix = out_index + (S.slot_first[p0] + c * E); // slots < 2^31
+                for (uint32_t e = 0; e < E; ++e)
+                    n += ix[e] != kHole;
+            });
+    }
+    uint32_t total;
+    const uint32_t before = block_scan(n, &total);
+    if (g < G)
+        local[g] = before;
+    if (threadIdx.x == 0) {
+        blk[blockIdx.x] = single ? 0u : total;
+        if (single) {
+            first_of[G] = total;
+            *n_out = total;
+        }
+    }
+}
+
+// (D.E and D.divE are not used: the section's own)
+__global__ __launch_bounds__(kBlock) void k_deliver_each(const SectEach S, const Deliver D)
+{
+    uint32_t s, chunk = 0;
+    const bool header = blockIdx.x < D.hdr_blocks;
+    if (header) {
+        uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+        if (t < D.G) {
+            D.first_of[t] = D.local[t] + D.blk[t / kBlock];
+            return;
+        }
+        t -= D.G;
+        if (t >= D.n_slots)
+            return;
+        s = t;
+    } else {
+        const uint32_t t = (blockIdx.x - D.hdr_blocks) * kBlock + threadIdx.x;
+        if (t >= D.n_pay)
+            return;
+        s = fdiv(t, D.divCD);
+        chunk = t - s * D.cd;
+    }
+    if (D.out_index[s] == kHole)
+        return;
+    uint32_t g = kNone, e = 0, row0 = 0; // the group of the slot's row, the slot within it, the row's first slot
+    for_plan(section_of(S.slot_first, S.n_plans, s), [&](uint32_t p) {
+        const uint32_t sf = S.slot_first[p], E = S.E[p], c = fdiv(s - sf, S.divE[p]);
+        e = s - sf - c * E;
+        row0 = s - e;
+        g = S.group_of[p][c]; // c < groups[p]: s < slot_first[p + 1]
+    });
+    if (g >= D.G)
+        return; // a row past the section's groups (RFEC_REGROUP_NONE), or a broken table: nothing is read by it
+    const uint8_t* ix = D.out_index + row0;
+    uint32_t j = D.local[g] + D.blk[g / kBlock]; // + the delivering slots of the row before this one
+    for (uint32_t q = 0; q < e; ++q)
+        j += ix[q] != kHole;
+    if (j >= D.max_out)
+        return;
+    if (header) {
+        const uint32_t* h = D.out_hdr + (size_t)s * 5;
+        uint32_t* r = D.seg + (size_t)j * kSegWords;
+#pragma unroll
+        for (int q = 0; q < 5; ++q)
+            r[q] = h[q];
+        r[5] = fec_id_of(D.fec_id0, g); // reserved = 0 in the high half
+    } else
+        st16(D.pay + (size_t)j * D.C + chunk, ld16(D.out_sh + (size_t)s * D.C + chunk));
+}
+
 } // namespace
 
 // The caller (rfec_recover_deliver.c) has checked n_plans in [1, 32], window_groups in [1, 65535], fec_id0 in
@@ -276,5 +378,69 @@ extern "C" int rfec_launch_recover_deliver(const rfec_regroup_section* sections,
     D.divCD = make_fastdiv(cd);
     RFEC_LAUNCH(k_deliver, dim3(D.hdr_blocks + blocks_for(D.n_pay)), dim3(kBlock), 0, st, S, D);
     rfec_set_indexed_path(5u | (single ? 2u : 3u) << 8);
+    return (int)hipGetLastError();
+}
+
+// rfec_recover_deliver_each (rfec_recover_deliver_each.c): the caller has checked what rfec_launch_recover_deliver's
+// has, per_group[p] >= 1 for every section with rows and slot_first[n_plans] * CD < 2^31; hipErrorInvalidValue
+// otherwise.  first, slot_first: host [n_plans + 1], the prefixes of the sections' rows and out slots.
+extern "C" int rfec_launch_recover_deliver_each(const rfec_regroup_section* sections, uint32_t n_plans,
+                                                const uint32_t* first, const uint32_t* slot_first,
+                                                const uint32_t* per_group, uint32_t groups, uint32_t fec_id0,
+                                                const uint8_t* shape_of, const uint32_t* rank_of, uint32_t stride,
+                                                uint32_t capacity, const uint8_t* out_shards, const rfec_hdr* out_hdr,
+                                                const uint8_t* out_index, uint32_t max_out, rfec_rx_seg* seg,
+                                                uint8_t* seg_payload, uint32_t* first_of, uint32_t* n_out,
+                                                void* workspace, void* stream)
+{
+    if (!n_plans || n_plans > kShapes || !groups || groups > 65535u || !fec_id0 || fec_id0 > 65535u || !stride ||
+        stride % 16 || capacity > stride || !first || !slot_first || !per_group)
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t cd = capacity ? (capacity + 15) / 16 : 1;
+    SectEach S = {};
+    S.n_plans = n_plans;
+    for (uint32_t p = 0; p < n_plans; ++p) {
+        const uint32_t rows = first[p + 1] - first[p], E = rows ? per_group[p] : 1u;
+        if (first[p + 1] < first[p] || !E || (uint64_t)slot_first[p] + (uint64_t)rows * E != slot_first[p + 1])
+            return (int)hipErrorInvalidValue;
+        S.first[p] = first[p];
+        S.slot_first[p] = slot_first[p];
+        S.E[p] = E;
+        S.divE[p] = make_fastdiv(E);
+        S.group_of[p] = sections[p].group_of;
+    }
+    S.first[n_plans] = first[n_plans];
+    const uint32_t n_slots = S.slot_first[n_plans] = slot_first[n_plans];
+    if ((uint64_t)n_slots * cd >= (1ull << 31))
+        return (int)hipErrorInvalidValue;
+    const uint32_t n_blk = blocks_for(groups);
+    uint32_t* local = static_cast<uint32_t*>(workspace);
+    uint32_t* blk = local + ((groups + 3u) & ~3u);
+    const uint32_t single = n_blk == 1;
+    RFEC_LAUNCH(k_deliver_count_each, dim3(n_blk), dim3(kBlock), 0, st, S, groups, shape_of, rank_of, out_index, local,
+                blk, first_of, n_out, single);
+    if (!single)
+        RFEC_LAUNCH(k_deliver_totals, dim3(1), dim3(kBlock), 0, st, blk, n_blk, groups, first_of, n_out);
+    Deliver D = {};
+    D.out_sh = reinterpret_cast<const v4u*>(out_shards);
+    D.out_hdr = reinterpret_cast<const uint32_t*>(out_hdr);
+    D.out_index = out_index;
+    D.seg = reinterpret_cast<uint32_t*>(seg);
+    D.pay = reinterpret_cast<v4u*>(seg_payload);
+    D.first_of = first_of;
+    D.local = local;
+    D.blk = blk;
+    D.G = groups;
+    D.C = stride / 16;
+    D.cd = cd;
+    D.max_out = max_out;
+    D.fec_id0 = fec_id0;
+    D.n_slots = max_out ? n_slots : 0u; // max_out == 0: no entry is written, and the scan is all there is
+    D.n_pay = D.n_slots * cd;
+    D.hdr_blocks = blocks_for((uint64_t)groups + D.n_slots);
+    D.divCD = make_fastdiv(cd);
+    RFEC_LAUNCH(k_deliver_each, dim3(D.hdr_blocks + blocks_for(D.n_pay)), dim3(kBlock), 0, st, S, D);
+    rfec_set_indexed_path(10u | (single ? 2u : 3u) << 8);
     return (int)hipGetLastError();
 }

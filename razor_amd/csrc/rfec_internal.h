@@ -282,6 +282,16 @@ int rfec_launch_recover_indexed_window(const rfec_kplan* plans, uint32_t n_plans
  * 0 for a refused plan */
 uint32_t rfec_recover_window_blocks(const rfec_kplan* P, uint32_t groups, uint32_t per_group, uint32_t cd,
                                     uint32_t n_rows);
+/* rfec_recover_indexed_window_each_out (rfec_recover_indexed_window_each.c, kernel in rfec_cascade.hip): that launch
+ * with per_group[p] out slots a row in section p (host [n_plans]; read only where groups[p] > 0), the sections' slots
+ * packed end to end: one launch of k_decode_window_each.  The caller has checked what rfec_launch_recover_indexed_window's
+ * has, per section with its own per_group[p] in [1, k], and the slots' total x CD < 2^31; hipErrorInvalidValue
+ * otherwise. */
+int rfec_launch_recover_indexed_window_each(const rfec_kplan* plans, uint32_t n_plans,
+                                            const rfec_regroup_section* sections, const uint32_t* groups,
+                                            uint32_t stride, uint32_t capacity, const uint8_t* rows, uint32_t n_rows,
+                                            uint64_t* recovered, const uint32_t* per_group, uint8_t* out_shards,
+                                            rfec_hdr* out_hdr, uint8_t* out_index, void* stream);
 /* rfec_recover_deliver (rfec_recover_deliver.c, kernels in rfec_deliver.hip): the outputs of
  * rfec_launch_recover_indexed_shapes as a dense list in window order, in three launches on `stream` (k_deliver_count,
  * k_deliver_totals, k_deliver), two when groups <= 256 (one block counts the window and writes the totals).  first:
@@ -295,10 +305,24 @@ int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n
                                 const rfec_hdr* out_hdr, const uint8_t* out_index, uint32_t max_out, rfec_rx_seg* seg,
                                 uint8_t* seg_payload, uint32_t* first_of, uint32_t* n_out, void* workspace,
                                 void* stream);
+/* rfec_recover_deliver_each (rfec_recover_deliver_each.c, kernels in rfec_deliver.hip): rfec_launch_recover_deliver
+ * over the outputs of rfec_launch_recover_indexed_window_each: k_deliver_count_each, k_deliver_totals, k_deliver_each,
+ * the same launches and workspace.  first, slot_first: host [n_plans + 1], the prefixes of the sections' rows and of
+ * their out slots; per_group: host [n_plans], read only for a section with rows and there >= 1.  The caller has
+ * checked what rfec_launch_recover_deliver's has, with slot_first[n_plans] * CD < 2^31; hipErrorInvalidValue
+ * otherwise. */
+int rfec_launch_recover_deliver_each(const rfec_regroup_section* sections, uint32_t n_plans, const uint32_t* first,
+                                     const uint32_t* slot_first, const uint32_t* per_group, uint32_t groups,
+                                     uint32_t fec_id0, const uint8_t* shape_of, const uint32_t* rank_of,
+                                     uint32_t stride, uint32_t capacity, const uint8_t* out_shards,
+                                     const rfec_hdr* out_hdr, const uint8_t* out_index, uint32_t max_out,
+                                     rfec_rx_seg* seg, uint8_t* seg_payload, uint32_t* first_of, uint32_t* n_out,
+                                     void* workspace, void* stream);
 /* Which kernels the calling thread's last rfec_launch_recover_indexed, rfec_launch_recover_indexed_matrix,
  * rfec_launch_recover_indexed_matrix_wide, rfec_launch_recover_indexed_rows_wide, rfec_launch_recover_indexed_shapes,
- * rfec_launch_recover_indexed_window or rfec_launch_recover_deliver took (host-side, thread-local, for tests; apart
- * from rfec_last_path, whose kinds are a closed table): 0 none yet,
+ * rfec_launch_recover_indexed_window, rfec_launch_recover_deliver, rfec_launch_recover_indexed_window_each or
+ * rfec_launch_recover_deliver_each took (host-side, thread-local, for tests; apart from rfec_last_path, whose kinds
+ * are a closed table): 0 none yet,
  * 1 | K << 8 one launch of k_decode_rows_indexed<K, 4> (K = 10, 32, or 0 for k and col at run time), 2 | MAXC << 8
  * k_peel_lds + k_recover_indexed<MAXC, ...> (MAXC = 4, 8), 3 | K << 8 one launch of k_decode_matrix_indexed<K, col>
  * (K = 6..16; rfec_launch_recover_indexed_matrix only), 4 | n << 8 one launch of k_decode_shapes_indexed over n
@@ -307,7 +331,10 @@ int rfec_launch_recover_deliver(const rfec_regroup_section* sections, uint32_t n
  * 6 | k << 8 one launch of k_decode_matrix_wide (k = 6..128; rfec_launch_recover_indexed_matrix_wide only),
  * 7 | k << 8 | col << 16 one launch of k_decode_rows_wide (k = 2..128 in rows of col = 2..128;
  * rfec_launch_recover_indexed_rows_wide only), 8 | n << 8 one launch of k_decode_window_indexed over n sections
- * with groups (rfec_launch_recover_indexed_window only). */
+ * with groups (rfec_launch_recover_indexed_window only), 9 | n << 8 one launch of k_decode_window_each over n
+ * sections with groups (rfec_launch_recover_indexed_window_each only), 10 | n << 8 the n = 2 or 3 launches of
+ * rfec_launch_recover_deliver_each (k_deliver_count_each, k_deliver_totals for a window of more than 256 groups,
+ * k_deliver_each). */
 uint32_t rfec_indexed_last_path(void);
 /* Which kernel the calling thread's last wire-codec launch (rfec_wire.hip: the rfec_launch_wire_* shims) took, and on
  * how many blocks: kernel id | grid blocks << 8, 0 before the first (host-side, thread-local, for tests; apart from

@@ -292,6 +292,16 @@ _SIGS = {
     "rfec_recover_deliver": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
                                        C.POINTER(C.c_uint32), C.c_uint32, C.c_uint16, _P, _P, C.c_uint32, C.c_uint32,
                                        C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "rfec_recover_indexed_window_each_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32,
+                                                       C.POINTER(rfec_regroup_section), C.POINTER(C.c_uint32),
+                                                       C.c_uint32, C.c_uint32, _P, C.c_uint32, _P,
+                                                       C.POINTER(C.c_uint32), _P, _P, _P, _P]),
+    "rfec_recover_window_slots": (C.c_uint64, [C.POINTER(rfec_regroup_section), C.c_uint32, C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32)]),
+    "rfec_recover_deliver_each": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
+                                            C.POINTER(C.c_uint32), C.c_uint32, C.c_uint16, _P, _P, C.c_uint32,
+                                            C.c_uint32, C.POINTER(C.c_uint32), _P, _P, _P, C.c_uint32, _P, _P, _P, _P,
+                                            _P, _P]),
     "rfec_sender_init": (None, [_P]),
     "rfec_sender_plan": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P]),
     "rfec_host_send_frames": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32,
@@ -355,6 +365,18 @@ def as_plan(p) -> rfec_plan:
     q = rfec_plan()
     C.memmove(C.byref(q), C.byref(p), C.sizeof(q))
     return q
+
+
+def window_first_slots(groups, per_group) -> tuple[list[int], list[int]]:
+    """The ragged numbering of rfec_recover_indexed_window_each_out and rfec_recover_deliver_each: (first,
+    slot_first), each [n_plans + 1]; first[p] is the sum of groups[q] over q < p and slot_first[p] the sum of
+    groups[q] * per_group[q] over q < p (per_group[q] of a section with groups[q] == 0 is not read).  Row c of
+    section p is output row first[p] + c; its out slot e is slot slot_first[p] + c * per_group[p] + e."""
+    first, slot_first = [0], [0]
+    for g, e in zip(groups, per_group):
+        first.append(first[-1] + int(g))
+        slot_first.append(slot_first[-1] + (int(g) * int(e) if g else 0))
+    return first, slot_first
 
 
 class Native:
@@ -683,6 +705,54 @@ class Native:
                                                   capacity, per_group, out_shards, out_hdr, out_index, max_out, seg,
                                                   seg_payload, first_of, n_out, workspace, stream),
                     "rfec_recover_deliver")
+
+    @staticmethod
+    def _window_arrays(plans, sections, groups, per_group):
+        if len(plans) != len(sections):
+            raise ValueError("one section per plan")
+        if groups is not None and len(groups) != len(plans):
+            raise ValueError("one group count per plan")
+        if per_group is not None and len(per_group) != len(plans):
+            raise ValueError("one per_group per plan")
+        pa = (rfec_plan * max(len(plans), 1))(*(as_plan(p) for p in plans))
+        sa = (rfec_regroup_section * max(len(sections), 1))(
+            *(s if isinstance(s, rfec_regroup_section) else rfec_regroup_section(**s) for s in sections))
+        ga = None if groups is None else (C.c_uint32 * max(len(groups), 1))(*(int(g) for g in groups))
+        ea = None if per_group is None else (C.c_uint32 * max(len(per_group), 1))(*(int(e) for e in per_group))
+        return pa, sa, ga, ea
+
+    def recover_indexed_window_each_out(self, plans, sections, groups, stride, capacity, rows, n_rows, recovered,
+                                        per_group, out_shards, out_hdr, out_index, stream=None):
+        """rfec_recover_indexed_window_each_out: recover_indexed_window_out with per_group a sequence, one out-slot
+        count per section.  The ragged numbering (window_first_slots): recovered is indexed by output row
+        first[p] + c; out_index, out_hdr and out_shards by slot slot_first[p] + c * per_group[p] + e, section p's
+        rows per_group[p] slots each and the sections' slots packed end to end."""
+        pa, sa, ga, ea = self._window_arrays(plans, sections, groups, per_group)
+        self._check(self.lib.rfec_recover_indexed_window_each_out(pa, len(plans), sa, ga, stride, capacity, rows,
+                                                                  n_rows, recovered, ea, out_shards, out_hdr,
+                                                                  out_index, stream),
+                    "rfec_recover_indexed_window_each_out")
+
+    def recover_window_slots(self, sections, groups, per_group) -> int:
+        """rfec_recover_window_slots: S, the out slots the three slot arrays of recover_indexed_window_each_out
+        hold: the sum of groups[p] * per_group[p] (groups[p] = sections[p].cap when groups is None)."""
+        n = len(per_group)
+        sa = None if sections is None else (rfec_regroup_section * max(len(sections), 1))(
+            *(s if isinstance(s, rfec_regroup_section) else rfec_regroup_section(**s) for s in sections))
+        ga = None if groups is None else (C.c_uint32 * max(len(groups), 1))(*(int(g) for g in groups))
+        ea = (C.c_uint32 * max(n, 1))(*(int(e) for e in per_group))
+        return int(self.lib.rfec_recover_window_slots(sa, n, ga, ea))
+
+    def recover_deliver_each(self, plans, sections, groups, G, fec_id0, shape_of, rank_of, stride, capacity,
+                             per_group, out_shards, out_hdr, out_index, max_out, seg, seg_payload, first_of, n_out,
+                             workspace, stream=None):
+        """rfec_recover_deliver_each: recover_deliver over what recover_indexed_window_each_out wrote, per_group the
+        same sequence, the slot arrays in the ragged numbering; workspace: recover_deliver_workspace_size(G)."""
+        pa, sa, ga, ea = self._window_arrays(plans, sections, groups, per_group)
+        self._check(self.lib.rfec_recover_deliver_each(pa, len(plans), sa, ga, G, fec_id0, shape_of, rank_of, stride,
+                                                       capacity, ea, out_shards, out_hdr, out_index, max_out, seg,
+                                                       seg_payload, first_of, n_out, workspace, stream),
+                    "rfec_recover_deliver_each")
 
     # -- sender staging (host memory) -------------------------------------------
     def sender_init(self):
