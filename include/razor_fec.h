@@ -163,6 +163,20 @@ int rfec_plan_from_fraction(uint16_t k, uint8_t protect_fraction, unsigned layer
  * consecutive segments, columns strided by `col`). */
 int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec_plan* plan);
 
+/* The plan a receiver takes for a SIM_FEC's (count, row, col), the only place
+ * a group's shape reaches it (rfec_wire_window_census reports these keys).  A
+ * key is plannable when 1 <= count <= RFEC_MAX_K, row >= 1, col >= 2 and
+ * row * col >= count; any other key gets RFEC_EINVAL.  If count >= 6 and
+ * rfec_num_packets(count, 255, ...) returns exactly (row, col) -- the planner's
+ * matrix-mode shape, the matrix key of count -- the plan is
+ * rfec_plan_matrix(count, row, col, RFEC_LAYER_ROWS | RFEC_LAYER_COLS); for any
+ * other key it is rfec_plan_matrix(count, row, col, RFEC_LAYER_ROWS).  A
+ * strip-mode sender whose key coincides with the matrix key gets the full
+ * matrix: its column parities simply never arrive, and the recovery is the
+ * same.  A plannable key whose plan has no lines (count 1) returns RFEC_OK with
+ * n_lines == 0. */
+int rfec_plan_from_key(uint16_t count, uint8_t row, uint8_t col, rfec_plan* plan);
+
 /*
  * Device layout (G groups, k segments, n = plan->n_lines):
  *   shards  [G][k][stride] u8    payloads, bytes beyond data_size MUST be 0
@@ -858,6 +872,84 @@ int rfec_wire_regroup_shapes(const rfec_plan* plans, uint32_t n_plans,
                              uint32_t n, const rfec_wire_rec* recs, uint32_t capacity,
                              uint8_t* shape_of, uint32_t* rank_of, uint32_t* anchor_of,
                              uint32_t* counts, int32_t* slot_of, void* stream);
+
+/*
+ * The census of a parsed window, on the device: which shapes occur in it, in
+ * window order, and how many groups each has -- what rfec_wire_regroup_shapes
+ * and the decodes behind it take as host arguments (plans, cap, groups), and
+ * what a receiver cannot know ahead: the flex sender picks (k, row, col) per
+ * frame, and the shape reaches the receiver only inside the SIM_FEC records.
+ * The census is 576 bytes: one small copy to the host replaces the copy of the
+ * n 64-byte records, or sections sized for the worst case and a read-back of
+ * counts.  From it the host builds the plans (rfec_plan_from_key of each
+ * shape), sizes every section exactly (cap = groups[p] = shape[p].groups) and
+ * runs the rest of the chain with no further read-back.
+ *
+ * (fec_id0, groups) is the caller's admission window, as rfec_wire_regroup_shapes
+ * takes it: the next expected id, and up to 65,535 groups.  recs [n], census,
+ * anchor_of [groups] and key_of [groups] are device pointers.
+ *
+ * The rule, independent of how the device schedules the work:
+ *  1. ENOTFEC, EWINDOW.  Rules 1 and 2 of rfec_wire_regroup, unchanged.
+ *     n_notfec and n_window count those records.
+ *  2. In-window records.  An in-window SIM_SEG counts in n_seg.  An in-window
+ *     SIM_FEC is accepted when its key (count, row, col) is plannable
+ *     (rfec_plan_from_key), its index is the index of a line of the key's plan
+ *     and data_size <= capacity.  Accepted records count in n_fec, the others
+ *     in n_refused.
+ *  3. Window extent.  g_first is the least group index over all in-window
+ *     records, or RFEC_REGROUP_NONE with none; g_end is 1 + the greatest, or 0
+ *     with none.  The caller tightens (fec_id0, groups) with them.
+ *  4. Anchor and key.  anchor_of[g] is the lowest arrival index among group
+ *     g's accepted SIM_FECs, or RFEC_REGROUP_NONE.  key_of[g] is
+ *     k | row << 8 | col << 16 of that record, or RFEC_REGROUP_NONE.  anchored
+ *     is the number of groups with an anchor.
+ *  5. Shapes.  The distinct keys among key_of are ordered by first_g, the least
+ *     g with that key -- window order, not arrival order.  n_shapes =
+ *     min(distinct, RFEC_CENSUS_MAX_SHAPES); shape[i] for i < n_shapes are the
+ *     keys with the least first_g, in that order; shape[i].groups is the number
+ *     of groups with that key.  other_groups counts the anchored groups whose
+ *     key is not listed: other_groups > 0 means more than 32 shapes (key_of
+ *     lets a caller run a second pass).  Entries i >= n_shapes and all reserved
+ *     words are 0: the whole struct is written on every call.
+ *
+ * Equivalence.  When other_groups == 0, take plans[i] =
+ * rfec_plan_from_key(shape[i]) in any order.  rfec_wire_regroup_shapes on the
+ * same (groups, fec_id0, n, recs, capacity) then writes the same anchor_of; its
+ * shape_of[g] is the index of key_of[g]'s plan, and 0xFF where the key is NONE;
+ * its counts[p] equals the groups of plans[p]'s shape.  (The regroup's accepted
+ * set is a subset of the census's, and every census anchor's key is among the
+ * plans: so each group's lowest accepted arrival is the same record.)
+ *
+ * Checked before any runtime call (RFEC_EINVAL, rfec_last_error names the
+ * argument): fec_id0 != 0, groups <= 65535, n <= 0x7FFFFFFF, capacity <= 65535,
+ * NULL pointers (recs may be NULL when n == 0) and alignment: 16 bytes recs and
+ * census, 4 bytes anchor_of and key_of.  groups == 0 touches nothing: every
+ * pointer may be NULL.  n == 0 writes the empty census (g_first NONE, all else
+ * 0) and both arrays (NONE).  The buffers must not overlap (not checked).  The
+ * call allocates nothing, copies nothing from the host, does not synchronise
+ * and launches only on `stream`: at most four launches (three with n == 0),
+ * none waiting on another workgroup.  census holds intermediate values until
+ * the last one has run.
+ */
+#define RFEC_CENSUS_MAX_SHAPES 32
+typedef struct {
+    uint16_t k;           /* the key: SIM_FEC count, row, col */
+    uint8_t row, col;
+    uint32_t groups;      /* groups of the window with this key */
+    uint32_t first_g;     /* the least of them */
+    uint32_t reserved;
+} rfec_census_shape; /* 16 bytes */
+typedef struct {
+    uint32_t n_shapes, other_groups, anchored, g_first, g_end;
+    uint32_t n_seg, n_fec, n_refused, n_notfec, n_window, reserved[6];
+    rfec_census_shape shape[RFEC_CENSUS_MAX_SHAPES];
+} rfec_window_census; /* 64 + 512 bytes, DEVICE */
+
+int rfec_wire_window_census(uint32_t groups, uint16_t fec_id0,
+                            uint32_t n, const rfec_wire_rec* recs, uint32_t capacity,
+                            rfec_window_census* census,
+                            uint32_t* anchor_of, uint32_t* key_of, void* stream);
 
 /*
  * rfec_recover_batch_out with shards and parity replaced by a row pool and a

@@ -31,7 +31,7 @@ ARCH = os.environ.get("RFEC_OFFLOAD_ARCH", "gfx950")
 # are a unit each, reached through the host functions rfec_families.h declares
 HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused", "cascade", "helpers", "probe",
                                              "wire", "fill", "service", "hostio", "regroup", "regroup_shapes",
-                                             "deliver", "matrix_wide", "rows_wide")]
+                                             "deliver", "matrix_wide", "rows_wide", "census")]
 # built once per SIM_VIDEO_SIZE: the C host layer, by concern (rfec_host.c: errors, planner, batched device
 # and wire API; rfec_dropin.c: drop-in symbols + resident service; rfec_hostmem.c: host-memory batches;
 # rfec_sender.c: sender staging; the receiver: rfec_rx_sim.c one shard's arrival-order control plane,
@@ -40,6 +40,7 @@ HIP_SRC = [CSRC / f"rfec_{u}.hip" for u in ("kernels", "encode", "peel", "fused"
 # drop-in; rfec_packed_matrix.c (the packed matrix records' entry points) and rfec_wire_fused.c (the fused encode +
 # SIM_FEC framing's), rfec_wire_regroup.c (parsed datagrams into the batch layout, its index-only form and the index-only form over
 # a window of several shapes) and
+# rfec_wire_census.c (a window's shapes and their group counts, kernels in rfec_census.hip) and
 # rfec_recover_indexed.c (the dense decode through a row map), rfec_recover_indexed_matrix.c (its one-launch form
 # for the sender's matrix plans of k = 6..16; rfec_recover_indexed_matrix_wide.c: for those of any k = 6..128, kernel
 # in rfec_matrix_wide.hip; rfec_recover_indexed_rows_wide.c: for a row layout of any width, kernel in
@@ -61,12 +62,12 @@ C_SRC = [CSRC / f for f in HOST_SRC] + [CSRC / "rfec_flex.c", CSRC / "rfec_packe
                                           CSRC / "rfec_recover_indexed_rows_wide.c",
                                           CSRC / "rfec_recover_indexed_window.c",
                                           CSRC / "rfec_recover_indexed_window_each.c",
-                                          CSRC / "rfec_recover_deliver_each.c"]
+                                          CSRC / "rfec_recover_deliver_each.c", CSRC / "rfec_wire_census.c"]
 NET_SRC = CSRC / "rfec_net.c"  # host-only (sockets), independent of SIM_VIDEO_SIZE
 HEADERS = [INCLUDE / "razor_fec.h", INCLUDE / "razor_flex.h", CSRC / "rfec_internal.h", CSRC / "rfec_launch.h",
            CSRC / "rfec_host_internal.h", CSRC / "rfec_device.h", CSRC / "rfec_families.h",
            CSRC / "rfec_row_blocks.h", CSRC / "rfec_regroup_rules.h", CSRC / "rfec_u128.h",
-           CSRC / "rfec_matrix_wide_blocks.h", CSRC / "rfec_rows_wide_blocks.h"]
+           CSRC / "rfec_matrix_wide_blocks.h", CSRC / "rfec_rows_wide_blocks.h", CSRC / "rfec_census_rules.h"]
 # the receiver units' own headers: only the C host layer includes them
 HOST_HEADERS = HEADERS + [CSRC / f"rfec_rx_{u}.h" for u in ("map", "sim", "pool", "plane", "dev")]
 

@@ -36,6 +36,7 @@
 #include "razor_fec.h"
 #include "rfec_internal.h"
 #include "rfec_host_internal.h"
+#include "rfec_census_rules.h"
 
 /* ------------------------------------------------------------------------ */
 /* errors                                                                    */
@@ -177,6 +178,29 @@ int rfec_plan_matrix(uint16_t k, uint8_t row, uint8_t col, unsigned layers, rfec
     if (row == 0 || col == 0 || (uint32_t)row * col < k)
         return set_err(RFEC_EINVAL, "row*col must cover k", 0);
     return build_plan(k, row, col, 1, layers, plan);
+}
+
+/* the plan a receiver takes for a SIM_FEC's (count, row, col): rfec_census_rules.h */
+int rfec_plan_from_key(uint16_t count, uint8_t row, uint8_t col, rfec_plan* plan)
+{
+    if (!plan)
+        return set_err(RFEC_EINVAL, "plan is NULL", 0);
+    if (!rfec_census_plannable(count, row, col))
+        return set_err(RFEC_EINVAL, "key is not plannable: 1 <= count <= RFEC_MAX_K, row >= 1, col >= 2 and "
+                                    "row*col >= count", 0);
+    uint8_t mrow = 0, mcol = 0;
+    rfec_num_packets(count, 255, &mrow, &mcol);
+    const unsigned layers = rfec_census_matrix_key(count, row, col, mrow, mcol) ? RFEC_LAYER_ROWS | RFEC_LAYER_COLS
+                                                                                 : RFEC_LAYER_ROWS;
+    return rfec_plan_matrix(count, row, col, layers, plan);
+}
+
+void rfec_census_lines_of_key(uint16_t count, uint8_t row, uint8_t col, uint8_t line_of[256])
+{
+    uint8_t mrow = 0, mcol = 0;
+    rfec_num_packets(count <= RFEC_MAX_K ? count : 0, 255, &mrow, &mcol);
+    for (uint32_t index = 0; index < 256; ++index)
+        line_of[index] = (uint8_t)rfec_census_line_of(count, row, col, index, mrow, mcol);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -195,6 +195,21 @@ int rfec_launch_wire_regroup_shapes(const rfec_kplan* plans, uint32_t n_plans, c
                                     uint32_t groups, uint32_t fec_id0, uint32_t n, const rfec_wire_rec* recs,
                                     uint32_t capacity, uint8_t* shape_of, uint32_t* rank_of, uint32_t* anchor_of,
                                     uint32_t* counts, int32_t* slot_of, void* stream);
+/* rfec_wire_window_census (rfec_wire_census.c, kernels in rfec_census.hip): the call's four launches on `stream`
+ * (three with n == 0: no record pass).  The matrix (row, col) of every count, from rfec_num_packets(count, 255), is
+ * made once per process and travels in the argument block.  The caller has checked groups in [1, 65535], n < 2^31,
+ * fec_id0 != 0, capacity <= 65535 and the pointers; hipErrorInvalidValue otherwise. */
+int rfec_launch_wire_census(uint32_t groups, uint32_t fec_id0, uint32_t n, const rfec_wire_rec* recs,
+                            uint32_t capacity, rfec_window_census* census, uint32_t* anchor_of, uint32_t* key_of,
+                            void* stream);
+/* For tests: the line of rfec_plan_from_key's plan that each SIM_FEC index 0..255 names under the key (count, row,
+ * col), or 0xFF -- rfec_census_rules.h's rule as the census kernels apply it; an unplannable key has no lines. */
+void rfec_census_lines_of_key(uint16_t count, uint8_t row, uint8_t col, uint8_t line_of[256]);
+/* For tests: the groups of one tile of k_census_shapes (one workgroup, a group per lane), and which launches the
+ * calling thread's last rfec_launch_wire_census made: launches (4, or 3 with n == 0) | tiles << 8, tiles =
+ * ceil(groups / tile); 0 before the first (host-side, thread-local, apart from the other tags). */
+uint32_t rfec_census_tile(void);
+uint32_t rfec_census_last_path(void);
 /* rfec_recover_indexed_out (rfec_recover_indexed.c, kernels in rfec_fused.hip / rfec_peel.hip): the dense decode with member and
  * parity rows read from rows [n_rows][stride] through src_of [G (k + n_lines)].  The caller has checked the plan
  * (k <= RFEC_MAX_K), stride a multiple of 16, capacity <= stride, out->per_group in [1, k],

@@ -161,6 +161,40 @@ class rfec_regroup_section(C.Structure):
 assert C.sizeof(rfec_regroup_section) == 72
 
 
+RFEC_CENSUS_MAX_SHAPES = 32
+CENSUS_TILE = 1024  # rfec_census_tile(): the groups of one tile of the census's shapes pass (rfec_census.hip)
+
+
+class rfec_census_shape(C.Structure):
+    """One shape of rfec_wire_window_census: the key (k, row, col), its groups and the least of them."""
+    _fields_ = [("k", C.c_uint16), ("row", C.c_uint8), ("col", C.c_uint8), ("groups", C.c_uint32),
+                ("first_g", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class rfec_window_census(C.Structure):
+    """rfec_wire_window_census's result (a device struct; from_bytes takes its 576 bytes copied to the host)."""
+    _fields_ = [("n_shapes", C.c_uint32), ("other_groups", C.c_uint32), ("anchored", C.c_uint32),
+                ("g_first", C.c_uint32), ("g_end", C.c_uint32), ("n_seg", C.c_uint32), ("n_fec", C.c_uint32),
+                ("n_refused", C.c_uint32), ("n_notfec", C.c_uint32), ("n_window", C.c_uint32),
+                ("reserved", C.c_uint32 * 6), ("shape", rfec_census_shape * RFEC_CENSUS_MAX_SHAPES)]
+
+    @classmethod
+    def from_bytes(cls, raw):
+        return cls.from_buffer_copy(bytes(raw))
+
+    def shapes(self):
+        return [(s.k, s.row, s.col, s.groups, s.first_g) for s in self.shape[:self.n_shapes]]
+
+
+CENSUS_SHAPE_DTYPE = np.dtype([("k", "<u2"), ("row", "u1"), ("col", "u1"), ("groups", "<u4"), ("first_g", "<u4"),
+                               ("reserved", "<u4")])
+WINDOW_CENSUS_DTYPE = np.dtype([("n_shapes", "<u4"), ("other_groups", "<u4"), ("anchored", "<u4"), ("g_first", "<u4"),
+                                ("g_end", "<u4"), ("n_seg", "<u4"), ("n_fec", "<u4"), ("n_refused", "<u4"),
+                                ("n_notfec", "<u4"), ("n_window", "<u4"), ("reserved", "<u4", (6,)),
+                                ("shape", CENSUS_SHAPE_DTYPE, (RFEC_CENSUS_MAX_SHAPES,))])
+assert C.sizeof(rfec_census_shape) == 16 and C.sizeof(rfec_window_census) == 576 == WINDOW_CENSUS_DTYPE.itemsize
+
+
 RFEC_SEND_MAX_SHAPES = 32
 RFEC_SEND_MAX_LINES = 512  # the sum of n_lines over one call's plans
 
@@ -272,6 +306,8 @@ _SIGS = {
                                           _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rfec_wire_regroup_shapes": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.POINTER(rfec_regroup_section),
                                            C.c_uint32, C.c_uint16, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "rfec_plan_from_key": (C.c_int, [C.c_uint16, C.c_uint8, C.c_uint8, C.POINTER(rfec_plan)]),
+    "rfec_wire_window_census": (C.c_int, [C.c_uint32, C.c_uint16, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P]),
     "rfec_recover_indexed_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P, C.c_uint32,
                                            _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P]),
     "rfec_recover_indexed_matrix_out": (C.c_int, [C.POINTER(rfec_plan), C.c_uint32, C.c_uint32, C.c_uint32, _P,
@@ -430,6 +466,42 @@ class Native:
         p = rfec_plan()
         self._check(self.lib.rfec_plan_matrix(k, row, col, layers, C.byref(p)), "plan")
         return p
+
+    def plan_from_key(self, count: int, row: int, col: int):
+        """rfec_plan_from_key: the plan a receiver takes for a SIM_FEC's (count, row, col)."""
+        p = rfec_plan()
+        self._check(self.lib.rfec_plan_from_key(count, row, col, C.byref(p)), "rfec_plan_from_key")
+        return p
+
+    def plans_from_census(self, census):
+        """(plans, groups) of a census read back from the device (rfec_window_census, or its 576 bytes): the plan of
+        every listed shape, in window order, and the groups of each -- the plans, and the exact cap and groups[p], of
+        wire_regroup_shapes and the decodes behind it.  Complete when census.other_groups == 0."""
+        if not isinstance(census, rfec_window_census):
+            census = rfec_window_census.from_bytes(census)
+        shapes = census.shapes()
+        return [self.plan_from_key(k, row, col) for k, row, col, _, _ in shapes], [s[3] for s in shapes]
+
+    def census_lines_of_key(self, count: int, row: int, col: int) -> np.ndarray:
+        """rfec_census_lines_of_key (rfec_internal.h, for tests): [256] u8, the line of plan_from_key's plan that
+        each SIM_FEC index names under the key as the census kernels decide it, or 0xFF."""
+        f = self.lib.rfec_census_lines_of_key
+        f.restype, f.argtypes = None, [C.c_uint16, C.c_uint8, C.c_uint8, _P]
+        out = np.empty(256, np.uint8)
+        f(count, row, col, out.ctypes.data)
+        return out
+
+    def census_last_path(self) -> int:
+        """rfec_census_last_path (rfec_internal.h, for tests): launches | tiles << 8 of the calling thread's last
+        wire_window_census, tiles = ceil(groups / CENSUS_TILE)."""
+        f = self.lib.rfec_census_last_path
+        f.restype, f.argtypes = C.c_uint32, []
+        return int(f())
+
+    def census_tile(self) -> int:
+        f = self.lib.rfec_census_tile
+        f.restype, f.argtypes = C.c_uint32, []
+        return int(f())
 
     # -- batched device API (pointers are device addresses as ints) ----------
     def encode_batch(self, plan, groups, stride, capacity, shards, hdr, parity, meta, fec_size, status,
@@ -606,6 +678,14 @@ class Native:
         self._check(self.lib.rfec_wire_regroup_shapes(pa, len(plans), sa, groups, fec_id0, n, recs, capacity, shape_of,
                                                       rank_of, anchor_of, counts, slot_of, stream),
                     "rfec_wire_regroup_shapes")
+
+    def wire_window_census(self, groups, fec_id0, n, recs, capacity, census, anchor_of, key_of, stream=None):
+        """rfec_wire_window_census: the shapes of the window of `groups` fec_ids from fec_id0 among n parsed datagrams,
+        in window order, and the groups of each, into the device struct `census` (576 bytes: rfec_window_census /
+        WINDOW_CENSUS_DTYPE; plans_from_census takes it once copied to the host); anchor_of and key_of [groups] (u32)
+        are every group's first accepted parity and its k | row << 8 | col << 16."""
+        self._check(self.lib.rfec_wire_window_census(groups, fec_id0, n, recs, capacity, census, anchor_of, key_of,
+                                                     stream), "rfec_wire_window_census")
 
     def recover_indexed_out(self, plan, groups, stride, capacity, rows, n_rows, src_of, hdr, present, meta, fec_size,
                             parity_present, recovered, per_group, out_shards, out_hdr, out_index, workspace,
